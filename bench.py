@@ -17,15 +17,23 @@ Launch (driver contract):
     # N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
     #        --master-addr 127.0.0.1 bench.py --gpus N ...
 Rank 0 prints exactly one JSON line with the aggregate metric.
+
+A plain run does only what that line needs: set up, warm up, time the K
+steps, print.  ``--dump-outputs DIR`` additionally writes what the last timed
+step computed as ``DIR/<name>.npy`` (same arguments → same seeded inputs, so
+two builds can be compared output for output).  ``--full`` is where any
+measurement beyond the headline figure belongs; none exists at present.
 """
 
 from __future__ import annotations
 
 import argparse
 import json
+import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -40,7 +48,8 @@ def parse_args():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1,
                    help="world size (informational; actual size from env)")
-    p.add_argument("--steps", type=int, default=20)
+    p.add_argument("--steps", type=int, default=20,
+                   help="number of timed steps (>= 1)")
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--global-batch", type=int, default=32768)
     p.add_argument("--dim", type=int, default=768)
@@ -69,7 +78,56 @@ def parse_args():
     p.add_argument("--no-ddp", dest="ddp", action="store_false",
                    help="manual post-backward grad averaging instead "
                         "(the reference harness's scheme)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's "
+                        "outputs (loss, embeddings, gradients, updated "
+                        "parameters) as DIR/<name>.npy, float32, at most "
+                        "64 MB in all (large arrays: a fixed seeded row "
+                        "sample)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure (none at present: a plain run already "
+                        "does only what the result line needs)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
+
+
+# --dump-outputs budget: 64 MB in all, shared evenly by the six arrays that
+# can be large (two embeddings, two tower weights, their two gradients); the
+# scalar loss parameters are a few bytes.
+_DUMP_MAX_ELEMS = (60 * 2 ** 20) // (6 * 4)
+
+
+def _dump_array(t: torch.Tensor) -> np.ndarray:
+    """float32 host copy; arrays over the per-array budget keep a fixed,
+    seeded, sorted sample of their rows."""
+    t = t.detach()
+    if t.dim() >= 2 and t.numel() > _DUMP_MAX_ELEMS:
+        row = t[0].numel()
+        k = max(1, _DUMP_MAX_ELEMS // row)
+        idx = np.sort(np.random.RandomState(0).choice(
+            t.shape[0], size=k, replace=False))
+        t = t[torch.as_tensor(idx, device=t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(path, last, model, loss_mod):
+    """Write what the last timed step handed its caller: the loss, both
+    embedding batches, every gradient and every updated parameter."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": last["loss"], "image_emb": last["image_emb"],
+              "text_emb": last["text_emb"]}
+    named = [("model." + (n[7:] if n.startswith("module.") else n), p)
+             for n, p in model.named_parameters()]
+    named += [("loss." + n, p) for n, p in loss_mod.named_parameters()]
+    for n, p in named:
+        arrays["param." + n] = p
+        if p.grad is not None:
+            arrays["grad." + n] = p.grad
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), _dump_array(t))
 
 
 def main():
@@ -107,6 +165,7 @@ def main():
 
     use_graph = (args.graph and device == "cuda" and world == 1
                  and args.csv is None)
+    last = {}   # the latest step's outputs, kept only for --dump-outputs
 
     def step():
         # Graph mode needs stable grad buffers across replays.
@@ -115,6 +174,10 @@ def main():
             zi, zt = model(img_feats, txt_feats)
         with timer.phase("loss_fwd"):
             loss = loss_mod(zi, zt)
+        if args.dump_outputs:
+            # References only (no copy, no sync); under --graph these are
+            # the capture's static tensors, refreshed by every replay.
+            last.update(loss=loss, image_emb=zi, text_emb=zt)
         with timer.phase("backward"):
             loss.backward()
         with timer.phase("grad_avg"):
@@ -169,6 +232,9 @@ def main():
         if hops:
             print("# hop_stats_ms " + json.dumps(
                 {k: round(v, 4) for k, v in hops.items()}), file=sys.stderr)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model, loss_mod)
 
     ms_per_step = elapsed / args.steps * 1000.0
     pairs_per_sec = args.global_batch / (elapsed / args.steps)

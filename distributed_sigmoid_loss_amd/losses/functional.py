@@ -131,12 +131,13 @@ def chunk_loss_fwd(zimg, ztxt, t_prime, bias, diag_offset=None,
 
 def chunk_loss_bwd(zimg, ztxt, t_prime, bias, diag_offset, grad_output,
                    col_chunk=None, impl="auto", quant="bf16",
-                   on_dztxt=None):
+                   on_dztxt=None, qcache=None):
     """Gradients of :func:`chunk_loss_fwd` wrt (zimg, ztxt, t_prime, bias).
 
     ``on_dztxt(dztxt)`` (optional) is invoked as soon as the text gradient is
     materialized, before the image-gradient GEMM — lets a distributed caller
-    start its reduce-scatter while the remaining GEMM runs.
+    start its reduce-scatter while the remaining GEMM runs.  ``qcache`` is
+    the forward's ``ops.QuantCache`` (fp8/mixed; ignored on the torch path).
     """
     if impl == "auto":
         impl = "hip" if zimg.is_cuda else "torch"
@@ -144,7 +145,7 @@ def chunk_loss_bwd(zimg, ztxt, t_prime, bias, diag_offset, grad_output,
         from .. import ops
         return ops.siglip_bwd(zimg.contiguous(), ztxt.contiguous(), t_prime,
                               bias, diag_offset, grad_output, col_chunk,
-                              quant=quant, on_dztxt=on_dztxt)
+                              quant=quant, on_dztxt=on_dztxt, qcache=qcache)
     with torch.no_grad():
         out = _torch_bwd(zimg, ztxt, t_prime, bias, diag_offset, grad_output,
                          col_chunk)
@@ -156,7 +157,9 @@ def chunk_loss_bwd(zimg, ztxt, t_prime, bias, diag_offset, grad_output,
 class _FusedSigmoidLoss(torch.autograd.Function):
     """GPU path: hand-written HIP kernels.
 
-    Two backward regimes (`ops.save_g_enabled` picks):
+    Three backward regimes (`ops.save_g_enabled` and
+    `ops.save_g_banded_enabled` pick); backward is a three-way dispatch to
+    `ops.siglip_bwd_from_g` / `ops.siglip_bwd_banded` / `ops.siglip_bwd`:
 
     - **saved-g** (default when the slab fits — 2 GiB at the B=32k bf16
       headline config): forward runs the fwd+g kernel emitting loss, the
@@ -198,15 +201,15 @@ class _FusedSigmoidLoss(torch.autograd.Function):
                 qc = ops.quantize_fp8_rowwise_pair(zimg, ztxt)
             else:
                 qc = ops.quantize_fp8_pair(zimg, ztxt)
+        # Saved layout: the four inputs, the regime's own tensors, then the
+        # quantization cache's tensors (ctx.n_qc of them).
         if save_g:
             buf, g, gt = ops.siglip_fwd_g(zimg, ztxt, t_prime, bias,
                                           diag_offset, quant=quant,
                                           qcache=qc)
             out3 = ops.reduce_out3(buf)
             loss = out3[0].clone()
-            saved = (zimg, ztxt, t_prime, bias, out3, g) \
-                + ((gt,) if gt is not None else ()) \
-                + (qc if qc is not None else ())
+            regime = (out3, g) + ((gt,) if gt is not None else ())
         elif banded:
             step = ops.banded_col_step(b)
             buf = ops._out_buf(zimg.device)
@@ -223,17 +226,16 @@ class _FusedSigmoidLoss(torch.autograd.Function):
                 slabs.append(g_s)
             out3 = ops.reduce_out3(buf)
             loss = out3[0].clone()
-            ctx.band_step = step
-            saved = (zimg, ztxt, t_prime, bias, out3) + tuple(slabs)
+            regime = (out3,) + tuple(slabs)
         else:
             loss = ops.siglip_fwd(zimg, ztxt, t_prime, bias, diag_offset,
                                   quant=quant, qcache=qc)
-            saved = (zimg, ztxt, t_prime, bias) \
-                + (qc if qc is not None else ())
-        ctx.save_for_backward(*saved)
+            regime = ()
+        qts = qc.tensors() if qc is not None else ()
+        ctx.save_for_backward(zimg, ztxt, t_prime, bias, *regime, *qts)
+        ctx.n_qc = len(qts)
         ctx.saved_g = save_g
         ctx.banded = banded
-        ctx.has_gt = save_g and quant in ("fp8", "mixed")
         ctx.diag_offset = diag_offset
         ctx.col_chunk = col_chunk   # None → single slab when addressable
         ctx.quant = quant
@@ -242,47 +244,22 @@ class _FusedSigmoidLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         from .. import ops
-        zimg, ztxt, t_prime, bias = ctx.saved_tensors[:4]
-        if getattr(ctx, "banded", False):
-            out3 = ctx.saved_tensors[4]
-            slabs = ctx.saved_tensors[5:]
-            step = ctx.band_step
-            dev = zimg.device
-            tp32 = t_prime.detach().reshape(()).to(dev).float()
-            t_true = tp32.exp()
-            go = grad_output.detach().reshape(()).to(dev).float()
-            scale = go * t_true
-            dzimg_acc = torch.zeros_like(zimg, dtype=torch.float32)
-            dztxt = torch.empty_like(ztxt)
-            scale_c = scale.to(ztxt.dtype)
-            for k, g_s in enumerate(slabs):
-                j0 = k * step
-                j1 = min(j0 + step, ztxt.shape[0])
-                zt_s = ztxt[j0:j1]
-                dzimg_acc += ((g_s @ zt_s) * scale).float()
-                dztxt[j0:j1] = (g_s.T @ zimg) * scale_c
-            dzimg = dzimg_acc.to(zimg.dtype)
-            dt_prime = (out3[1] * go * t_true).to(
-                t_prime.dtype).reshape(t_prime.shape)
-            dbias = (out3[2] * go).to(bias.dtype).reshape(bias.shape)
+        saved = ctx.saved_tensors
+        inputs = saved[:4]
+        regime = saved[4:len(saved) - ctx.n_qc]
+        qc = (ops.QuantCache.from_tensors(saved[len(saved) - ctx.n_qc:])
+              if ctx.n_qc else None)
+        if ctx.banded:
+            grads = ops.siglip_bwd_banded(*inputs, grad_output, regime[0],
+                                          regime[1:])
         elif ctx.saved_g:
-            i = 4
-            out3, g = ctx.saved_tensors[i:i + 2]
-            i += 2
-            gt = None
-            if ctx.has_gt:
-                gt = ctx.saved_tensors[i]
-                i += 1
-            qc = ctx.saved_tensors[i:] or None
-            dzimg, dztxt, dt_prime, dbias = ops.siglip_bwd_from_g(
-                zimg, ztxt, t_prime, bias, grad_output, out3, g, gt,
-                quant=ctx.quant, qcache=qc)
+            out3, g, gt = (regime + (None,))[:3]
+            grads = ops.siglip_bwd_from_g(*inputs, grad_output, out3, g, gt,
+                                          quant=ctx.quant, qcache=qc)
         else:
-            qc = ctx.saved_tensors[4:] if len(ctx.saved_tensors) > 4 else None
-            dzimg, dztxt, dt_prime, dbias = ops.siglip_bwd(
-                zimg, ztxt, t_prime, bias, ctx.diag_offset, grad_output,
-                ctx.col_chunk, quant=ctx.quant, qcache=qc)
-        return dzimg, dztxt, dt_prime, dbias, None, None, None, None
+            grads = ops.siglip_bwd(*inputs, ctx.diag_offset, grad_output,
+                                   ctx.col_chunk, quant=ctx.quant, qcache=qc)
+        return grads + (None, None, None, None)
 
 
 def sigmoid_contrastive_loss(zimg: torch.Tensor, ztxt: torch.Tensor,

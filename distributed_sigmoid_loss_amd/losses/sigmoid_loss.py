@@ -123,7 +123,7 @@ class _RingAllGatherLoss(torch.autograd.Function):
         # scale — fwd/bwd loss surfaces differed at W>1).
         fp8_wire = quant == "fp8" and world > 1
         use_q = quant == "fp8" and on_gpu
-        qcaches = [None] * world        # per-source (zi_q, si, zt_q, st)
+        qcaches = [None] * world        # per-source ops.QuantCache
         if quant == "fp8":
             zi_q, si = _ops._quant_fp8(zimg)
             zt_q0, st0 = _ops._quant_fp8(ztxt)
@@ -132,7 +132,7 @@ class _RingAllGatherLoss(torch.autograd.Function):
                 return (q8.to(torch.float32) * sc).to(zimg.dtype)
 
             def qc_of(q8, sc):
-                return (zi_q, si, q8, sc.reshape(()))
+                return _ops.QuantCache(zi_q, q8, si, sc.reshape(()))
         else:
             zt_q0 = st0 = None
 
@@ -143,8 +143,7 @@ class _RingAllGatherLoss(torch.autograd.Function):
                 return None
             if zt_chunk is ztxt:
                 return qc_of(zt_q0, st0)
-            zt_q, st = _ops._quant_fp8(zt_chunk)
-            return (zi_q, si, zt_q, st)
+            return qc_of(*_ops._quant_fp8(zt_chunk))
 
         g_slab = gt_slab = out3 = None
         g_chunks = [None] * world       # fp8: per-chunk g (scales differ)
@@ -314,12 +313,11 @@ class _RingAllGatherLoss(torch.autograd.Function):
                     idx["gt_slab"] = len(extra)
                     extra.append(gt_slab)
         if use_q:
-            # per-source (zt_q, st) + the shared (zi_q, si)
-            idx["zi_q"] = len(extra)
-            extra += [zi_q, si]
-            idx["ztq"] = len(extra)
+            # one per-tensor cache per source (the image side is shared;
+            # saving the same tensor again costs nothing)
+            idx["qcaches"] = len(extra)
             for qc in qcaches:
-                extra += [qc[2], qc[3]]
+                extra += qc.tensors()
         ctx.save_for_backward(*saved, *extra)
         ctx.extra_idx = idx
         ctx.save_g = save_g
@@ -381,59 +379,45 @@ class _RingAllGatherLoss(torch.autograd.Function):
             dzimg, dtxt_flat, dt_prime, dbias = _ops.siglip_bwd_from_g(
                 zimg, all_txt, t_prime, bias, go, out3, g, gt,
                 quant=quant, qcache=qc, on_dztxt=on_dztxt)
-        elif ctx.save_g:
-            # fp8 saved-g: per-chunk g and scales (text side); the image
-            # side has one scale, so dztxt is still a single GEMM over the
-            # full gt slab.
-            zi_q, si = extra[idx["zi_q"]], extra[idx["zi_q"] + 1]
-            gt_slab = extra[idx["gt_slab"]]
-            tp32 = t_prime.detach().reshape(()).float()
-            t_true = tp32.exp()
-            go32 = go.detach().reshape(()).to(zimg.device).float()
-            scale = go32 * t_true
-            dtxt_flat = _ops.scaled_mm8(gt_slab, zi_q, (scale / 448.0) * si)
-            on_dztxt(dtxt_flat)
-            dzimg_acc = torch.zeros_like(zimg, dtype=torch.float32)
-            dt_acc = torch.zeros((), device=zimg.device, dtype=torch.float32)
-            db_acc = torch.zeros((), device=zimg.device, dtype=torch.float32)
-            for src in range(world):
-                zt_q = extra[idx["ztq"] + 2 * src]
-                st = extra[idx["ztq"] + 2 * src + 1]
-                g_c = extra[idx["g_chunks"] + src]
-                o3 = extra[idx["out3s"] + src]
-                dzimg_acc += _ops.scaled_mm8(
-                    g_c, zt_q, (scale / 448.0) * st).float()
-                dt_acc = dt_acc + o3[1] * (t_true * si * st)
-                db_acc = db_acc + o3[2]
-            dzimg = dzimg_acc.to(zimg.dtype)
-            dt_prime = (dt_acc * go32).to(t_prime.dtype).reshape(
-                t_prime.shape)
-            dbias = (db_acc * go32).to(bias.dtype).reshape(bias.shape)
-        elif quant == "fp8" and "ztq" in idx:
-            # fp8 recompute path: per-chunk backward with the forward's own
-            # per-chunk scales (never requantize — fwd/bwd must see the same
-            # quantized values).
-            zi_q, si = extra[idx["zi_q"]], extra[idx["zi_q"] + 1]
-            dzimg_acc = torch.zeros_like(zimg, dtype=torch.float32)
-            dtxt_flat = torch.empty((world * b, zimg.shape[1]),
-                                    device=zimg.device, dtype=zimg.dtype)
-            dt_prime = None
-            dbias = None
-            for src in range(world):
-                zt_q = extra[idx["ztq"] + 2 * src]
-                st = extra[idx["ztq"] + 2 * src + 1]
-                qc = (zi_q, si, zt_q, st)
-                diag = 0 if src == rank else None
-                dzi, dzt, dtp, dbs = chunk_loss_bwd(
-                    zimg, chunks[src], t_prime, bias, diag, go,
-                    col_chunk=ctx.col_chunk, impl=ctx.impl, quant=quant,
-                    qcache=qc)
-                dzimg_acc += dzi.float()
-                dtxt_flat[src * b:(src + 1) * b] = dzt
-                dt_prime = dtp if dt_prime is None else dt_prime + dtp
-                dbias = dbs if dbias is None else dbias + dbs
-            on_dztxt(dtxt_flat)
-            dzimg = dzimg_acc.to(zimg.dtype)
+        elif quant == "fp8" and "qcaches" in idx:
+            # fp8 keeps per-chunk text scales (never requantize — fwd/bwd
+            # must see the same quantized values), so both regimes walk the
+            # chunks with the forward's own per-source caches.
+            qts = extra[idx["qcaches"]:]
+            qcs = [_ops.QuantCache.from_tensors(qts[4 * s:4 * s + 4])
+                   for s in range(world)]
+            dt_prime = dbias = 0
+            if ctx.save_g:
+                # saved-g: the image side has one scale, so dztxt is still a
+                # single GEMM over the full gt slab.
+                g_chunks = extra[idx["g_chunks"]:idx["g_chunks"] + world]
+                out3s = extra[idx["out3s"]:idx["out3s"] + world]
+                go32 = go.detach().reshape(()).to(zimg.device).float()
+                t_true = t_prime.detach().reshape(()).float().exp()
+                dzimg, dtxt_flat = _ops.grad_gemms(
+                    [_ops.GBand(g_c, None, zt, qc)
+                     for g_c, zt, qc in zip(g_chunks, chunks, qcs)],
+                    zimg, world * b, go32 * t_true, on_dztxt=on_dztxt,
+                    gt_full=extra[idx["gt_slab"]])
+                for o3, qc in zip(out3s, qcs):
+                    dtp, dbs = _ops.scalar_grads(
+                        o3, go32, t_true * qc.si * qc.st, t_prime, bias)
+                    dt_prime, dbias = dt_prime + dtp, dbias + dbs
+            else:
+                dzimg_acc = torch.zeros_like(zimg, dtype=torch.float32)
+                dtxt_flat = torch.empty((world * b, zimg.shape[1]),
+                                        device=zimg.device, dtype=zimg.dtype)
+                for src in range(world):
+                    dzi, dzt, dtp, dbs = chunk_loss_bwd(
+                        zimg, chunks[src], t_prime, bias,
+                        0 if src == rank else None, go,
+                        col_chunk=ctx.col_chunk, impl=ctx.impl, quant=quant,
+                        qcache=qcs[src])
+                    dzimg_acc += dzi.float()
+                    dtxt_flat[src * b:(src + 1) * b] = dzt
+                    dt_prime, dbias = dt_prime + dtp, dbias + dbs
+                on_dztxt(dtxt_flat)
+                dzimg = dzimg_acc.to(zimg.dtype)
         else:
             # bf16/mixed recompute: one fused backward over the concatenated
             # (W·b, d) text block — identical math to per-chunk calls (diag

@@ -20,6 +20,13 @@ exposes:
 - fused tower helpers: :func:`l2_normalize` (single-pass fwd/bwd) and the
   fused fp8 quantizers.
 
+Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
+the only caller of the extension's single ``siglip_tile`` entry point; every
+backward regime (recompute, saved-g, banded saved-g, the fp8 ring) runs its
+two gradient GEMMs through :func:`grad_gemms` and its scalar gradients
+through :func:`scalar_grads`; a quantization made once per step travels as a
+:class:`QuantCache`.
+
 These are *loud* paths: calling them on a GPU without the built extension
 raises — there is no silent eager fallback on device (CPU fallbacks live in
 ``losses/functional.py`` and are CPU-only by construction).
@@ -28,8 +35,9 @@ raises — there is no silent eager fallback on device (CPU fallbacks live in
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -129,35 +137,16 @@ def _load():
         _lib_err = f"failed to load {SO_PATH}: {e}"
         return None
     lib.siglip_ext_abi.restype = ctypes.c_int
-    if lib.siglip_ext_abi() != 9:
+    if lib.siglip_ext_abi() != 10:
         _lib_err = (f"stale HIP extension at {SO_PATH} "
-                    f"(ABI {lib.siglip_ext_abi()}, need 9); rebuild with: "
+                    f"(ABI {lib.siglip_ext_abi()}, need 10); rebuild with: "
                     "python -m distributed_sigmoid_loss_amd.ops.build --force")
         return None
-    lib.siglip_fwd_bf16.restype = ctypes.c_int
-    lib.siglip_fwd_bf16.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int] * 5
-    lib.siglip_bwd_g_bf16.restype = ctypes.c_int
-    lib.siglip_bwd_g_bf16.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 5
-    lib.siglip_fwd_fp8.restype = ctypes.c_int
-    lib.siglip_fwd_fp8.argtypes = ([ctypes.c_void_p] * 6
-                                   + [ctypes.c_int] * 5
-                                   + [ctypes.c_void_p] * 2)
-    lib.siglip_bwd_g_fp8.restype = ctypes.c_int
-    lib.siglip_bwd_g_fp8.argtypes = ([ctypes.c_void_p] * 8
-                                     + [ctypes.c_int] * 5
-                                     + [ctypes.c_void_p] * 4)
-    lib.siglip_bwd_g_mixed.restype = ctypes.c_int
-    lib.siglip_bwd_g_mixed.argtypes = (
-        [ctypes.c_void_p] * 8 + [ctypes.c_int] * 5)
-    lib.siglip_fwdg_bf16.restype = ctypes.c_int
-    lib.siglip_fwdg_bf16.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int] * 6
-    lib.siglip_fwdg_mixed.restype = ctypes.c_int
-    lib.siglip_fwdg_mixed.argtypes = (
-        [ctypes.c_void_p] * 8 + [ctypes.c_int] * 6)
-    lib.siglip_fwdg_fp8.restype = ctypes.c_int
-    lib.siglip_fwdg_fp8.argtypes = ([ctypes.c_void_p] * 8
-                                    + [ctypes.c_int] * 6
-                                    + [ctypes.c_void_p] * 4)
+    # (stream, mode, eb, eb_g, 11 pointers, b, n, d, ldg, diag, flags)
+    lib.siglip_tile.restype = ctypes.c_int
+    lib.siglip_tile.argtypes = ([ctypes.c_void_p] + [ctypes.c_int] * 3
+                                + [ctypes.c_void_p] * 11
+                                + [ctypes.c_int] * 6)
     lib.l2norm_fwd_bf16.restype = ctypes.c_int
     lib.l2norm_fwd_bf16.argtypes = (
         [ctypes.c_void_p] * 4 + [ctypes.c_int] * 2 + [ctypes.c_float])
@@ -272,65 +261,150 @@ def rowwise_ok(b: int, n: int, d: int) -> bool:
     lose nothing.  Turn it on for embeddings with per-row dynamic range
     beyond e4m3's ~2^18 (see test_rowwise_quant_keeps_per_row_precision)."""
     return (os.environ.get("SIGLIP_FP8_ROWWISE", "0") == "1"
-            and b % 16 == 0 and n % 16 == 0 and d % 16 == 0
-            and hasattr(torch, "_scaled_mm"))
+            and _mm8_ok(b, d, n))
 
 
-def quantize_fp8_rowwise_pair(zimg: torch.Tensor, ztxt: torch.Tensor):
-    """Row-wise qcache: an 8-tuple (zi_q, zi_e8, zi_ratio, si_ref,
-    zt_q, zt_e8, zt_ratio, st_ref) — distinguished from the per-tensor
-    4-tuple by length."""
-    return _quant_fp8_rowwise(zimg) + _quant_fp8_rowwise(ztxt)
+@dataclasses.dataclass(frozen=True, eq=False)
+class QuantCache:
+    """One quantization of an (image, text) embedding pair, made once and
+    shared by forward and backward (``qcache=``).  Two policies:
+
+    - per-tensor: ``x ≈ q · s`` with fp32 scalars ``si`` / ``st``;
+    - row-wise (``rowwise``): per-row e8m0 exponents ``*_e8`` for the MX
+      MFMA's hardware dequant, per-row ``*_ratio`` for the slab folds, and
+      the tensor-max factors ``si_ref`` / ``st_ref`` the GEMM scale carries.
+    """
+    zi_q: torch.Tensor
+    zt_q: torch.Tensor
+    si: Optional[torch.Tensor] = None
+    st: Optional[torch.Tensor] = None
+    zi_e8: Optional[torch.Tensor] = None
+    zt_e8: Optional[torch.Tensor] = None
+    zi_ratio: Optional[torch.Tensor] = None
+    zt_ratio: Optional[torch.Tensor] = None
+    si_ref: Optional[torch.Tensor] = None
+    st_ref: Optional[torch.Tensor] = None
+
+    @property
+    def rowwise(self) -> bool:
+        return self.zi_e8 is not None
+
+    @property
+    def gemm_scales(self):
+        """(image, text) per-tensor factors the fp8 gradient GEMMs carry."""
+        return (self.si_ref, self.st_ref) if self.rowwise else (self.si,
+                                                                self.st)
+
+    def tensors(self) -> tuple:
+        """The populated fields, in field order (``save_for_backward``)."""
+        ts = (getattr(self, f.name) for f in dataclasses.fields(self))
+        return tuple(t for t in ts if t is not None)
+
+    @classmethod
+    def from_tensors(cls, ts) -> "QuantCache":
+        """Inverse of :meth:`tensors`: 4 tensors are a per-tensor cache, 8 a
+        row-wise one."""
+        ts = tuple(ts)
+        if len(ts) == 4:
+            return cls(*ts)
+        if len(ts) == 8:
+            return cls(ts[0], ts[1], None, None, *ts[2:])
+        raise ValueError(f"QuantCache takes 4 or 8 tensors, got {len(ts)}")
+
+    def text_rows(self, j0: int, j1: int) -> "QuantCache":
+        """The same (per-tensor) cache restricted to text rows j0:j1."""
+        return dataclasses.replace(self, zt_q=self.zt_q[j0:j1])
 
 
-def quantize_fp8_pair(zimg: torch.Tensor, ztxt: torch.Tensor):
+def quantize_fp8_rowwise_pair(zimg: torch.Tensor,
+                              ztxt: torch.Tensor) -> QuantCache:
+    zi_q, zi_e8, zi_ratio, si_ref = _quant_fp8_rowwise(zimg)
+    zt_q, zt_e8, zt_ratio, st_ref = _quant_fp8_rowwise(ztxt)
+    return QuantCache(zi_q, zt_q, zi_e8=zi_e8, zt_e8=zt_e8,
+                      zi_ratio=zi_ratio, zt_ratio=zt_ratio,
+                      si_ref=si_ref, st_ref=st_ref)
+
+
+def quantize_fp8_pair(zimg: torch.Tensor, ztxt: torch.Tensor) -> QuantCache:
     """Quantize both embedding tensors once; pass the result as ``qcache`` to
     both :func:`siglip_fwd` and :func:`siglip_bwd` so an fwd+bwd step pays a
     single quantization pass."""
     zi_q, si = _quant_fp8(zimg)
     zt_q, st = _quant_fp8(ztxt)
-    return zi_q, si, zt_q, st
+    return QuantCache(zi_q, zt_q, si, st)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _launch_tile(mode: int, quant: str, zi: torch.Tensor, zt: torch.Tensor,
+                 tp: torch.Tensor, bp: torch.Tensor, out: torch.Tensor,
+                 g: Optional[torch.Tensor] = None,
+                 gt: Optional[torch.Tensor] = None,
+                 diag_offset: Optional[int] = None, rowscales=None,
+                 default_gm: str = "4"):
+    """The one call into ``lib.siglip_tile``.  ``zi``/``zt`` are the operands
+    the kernel reads (bf16, or e4m3 for fp8 logits — their element size is
+    ``eb``).  ``g`` ``(b, n)`` / ``gt`` ``(n, b)`` are the output slabs
+    (``quant`` picks their element size ``eb_g``); they may be column / row
+    VIEWS into a wider slab — the view carries the column offset and its
+    row stride is the kernel's ``ldg`` — so torch's slicing, not pointer
+    arithmetic here, keeps a chunk inside its slab.  ``rowscales`` is the
+    row-wise policy's (a_e8, b_e8, a_rat, b_rat)."""
+    lib = _require_lib()
+    b, d = zi.shape
+    n = zt.shape[0]
+    eb_g = 1 if quant in ("fp8", "mixed") else 2
+    ldg = n
+    if g is not None:
+        ldg = g.stride(0)
+        if (g.shape != (b, n) or g.stride(1) != 1 or g.element_size() != eb_g
+                or (gt is not None and (gt.shape != (n, b)
+                                        or not gt.is_contiguous()))):
+            raise RuntimeError("g/gt slab layout does not match the block")
+        if b * ldg * eb_g >= 2 ** 32:
+            raise RuntimeError(
+                "g slab exceeds the kernel's 32-bit addressing; use the "
+                "recompute path (save_g_enabled would have said no)")
+    a_e8, b_e8, a_rat, b_rat = rowscales or (None,) * 4
+    stream = torch.cuda.current_stream(zi.device).cuda_stream
+    _check(lib.siglip_tile(
+        ctypes.c_void_p(stream), mode, zi.element_size(), eb_g,
+        _ptr(zi), _ptr(zt), _ptr(tp), _ptr(bp), _ptr(out), _ptr(g), _ptr(gt),
+        _ptr(a_e8), _ptr(b_e8), _ptr(a_rat), _ptr(b_rat),
+        b, n, d, ldg,
+        _DIAG_NONE if diag_offset is None else int(diag_offset),
+        _kernel_flags(default_gm)), f"siglip_tile(mode={mode}, {quant})")
+
+
+def _logit_operands(quant, zimg, ztxt, tp, qcache):
+    """What the tile kernel reads for ``quant``: (zi, zt, tp, rowscales).
+    fp8 logits read the quantized pair; per-tensor scales are folded into
+    the temperature (t_eff = t·s_img·s_txt), row-wise scales go to the MFMA
+    as e8m0 bytes and tp stays unmodified (acc is the true dot)."""
+    if quant != "fp8":
+        return zimg, ztxt, tp, None
+    qc = qcache if qcache is not None else quantize_fp8_pair(zimg, ztxt)
+    if qc.rowwise:
+        return qc.zi_q, qc.zt_q, tp, (qc.zi_e8, qc.zt_e8,
+                                      qc.zi_ratio, qc.zt_ratio)
+    return qc.zi_q, qc.zt_q, tp + qc.si.log() + qc.st.log(), None
 
 
 def siglip_fwd(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
                bias: torch.Tensor, diag_offset: Optional[int],
                quant: str = "bf16", qcache=None) -> torch.Tensor:
-    lib = _require_lib()
     _validate(zimg, ztxt, quant)
     if quant == "mixed":
         quant = "bf16"   # mixed = bf16 logits; fp8 applies to backward only
-    b, d = zimg.shape
-    n = ztxt.shape[0]
     dev = zimg.device
-    tp = _prep_scalar(t_prime, dev)
-    bp = _prep_scalar(bias, dev)
-    extra = ()
-    if quant == "fp8":
-        if qcache is not None and len(qcache) == 8:
-            # row-wise policy: hardware dequant, tp stays unmodified
-            zi_q, zi_e8, _, _, zt_q, zt_e8, _, _ = qcache
-            extra = (ctypes.c_void_p(zi_e8.data_ptr()),
-                     ctypes.c_void_p(zt_e8.data_ptr()))
-        else:
-            zi_q, si, zt_q, st = (qcache if qcache is not None
-                                  else quantize_fp8_pair(zimg, ztxt))
-            tp = tp + si.log() + st.log()
-            extra = (None, None)
-        zi_ptr, zt_ptr = zi_q.data_ptr(), zt_q.data_ptr()
-        fn = lib.siglip_fwd_fp8
-    else:
-        zi_ptr, zt_ptr = zimg.data_ptr(), ztxt.data_ptr()
-        fn = lib.siglip_fwd_bf16
+    zi_k, zt_k, tp_k, rowscales = _logit_operands(
+        quant, zimg, ztxt, _prep_scalar(t_prime, dev), qcache)
     buf = _out_buf(dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
-    _check(fn(
-        ctypes.c_void_p(stream),
-        ctypes.c_void_p(zi_ptr), ctypes.c_void_p(zt_ptr),
-        ctypes.c_void_p(tp.data_ptr()), ctypes.c_void_p(bp.data_ptr()),
-        ctypes.c_void_p(buf.data_ptr()), b, n, d, diag,
-        _kernel_flags(default_gm="8"), *extra),
-        "siglip_fwd")
+    _launch_tile(0, quant, zi_k, zt_k, tp_k, _prep_scalar(bias, dev), buf,
+                 diag_offset=diag_offset, rowscales=rowscales,
+                 default_gm="8")
     return buf[:, 0].sum()
 
 
@@ -347,48 +421,33 @@ def siglip_bwd(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
     invoked as soon as the text gradient exists so distributed callers can
     overlap their reduce-scatter with the remaining image-gradient GEMM.
     """
-    lib = _require_lib()
     _validate(zimg, ztxt, quant)
     b, d = zimg.shape
     n = ztxt.shape[0]
     dev = zimg.device
     tp = _prep_scalar(t_prime, dev)
     bp = _prep_scalar(bias, dev)
-    t_true = tp.exp()
-    if quant in ("fp8", "mixed"):
+    fp8g = quant in ("fp8", "mixed")   # g slabs are e4m3 (×448), plus gᵀ
+    qc = None
+    if fp8g:
         # Reuse the forward's quantization when provided (identical inputs
-        # give identical amax, so recomputing is equivalent but wasteful);
-        # the g kernel sees t_eff so its logits match the forward's.
-        # (The recompute path is per-tensor only — row-wise qcaches ride
-        # the saved-g path, ops.siglip_bwd_from_g.)
-        if qcache is not None and len(qcache) == 8:
+        # give identical amax, so recomputing is equivalent but wasteful).
+        # fp8 logits read it through t_eff so they match the forward's;
+        # mixed recomputes bf16 logits and quantizes for the GEMMs only.
+        # (The recompute path is per-tensor only — row-wise caches ride the
+        # saved-g path, siglip_bwd_from_g.)
+        if qcache is not None and qcache.rowwise:
             raise RuntimeError(
                 "row-wise fp8 qcache requires the saved-g backward")
-        zi_q, si, zt_q, st = (qcache if qcache is not None
-                              else quantize_fp8_pair(zimg, ztxt))
-        zi_g, zt_g = zi_q, zt_q           # fp8 GEMM operands
-        if quant == "fp8":
-            # fp8 logits: kernel reads quantized inputs with t_eff.
-            tp_k = tp + si.log() + st.log()
-            g_fn = lib.siglip_bwd_g_fp8
-            zi_k, zt_k = zi_q, zt_q
-        else:
-            # mixed: bf16 logits recompute; quantized inputs feed only the
-            # fp8 gradient GEMMs below.
-            tp_k = tp
-            g_fn = lib.siglip_bwd_g_mixed
-            zi_k, zt_k = zimg, ztxt
-    else:
-        tp_k = tp
-        g_fn = lib.siglip_bwd_g_bf16
-        zi_k, zt_k = zimg, ztxt
+        if b % 4 != 0:   # packed gt stores need b%4
+            raise RuntimeError(f"{quant} backward requires batch % 4 == 0")
+        qc = qcache if qcache is not None else quantize_fp8_pair(zimg, ztxt)
+    zi_k, zt_k, tp_k, _ = _logit_operands(quant, zimg, ztxt, tp, qc)
     scal = _out_buf(dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
 
     # Column slab sizing: the kernel's g-store addressing is 32-bit, so
     # b * slab * esz bytes must stay below 2^32; beyond that (and to bound
     # workspace at huge n) we chunk.
-    fp8g = quant in ("fp8", "mixed")   # g slabs are e4m3 (×448)
     g_esz = 1 if fp8g else 2
     g_dtype = torch.float8_e4m3fn if fp8g else torch.bfloat16
     step = col_chunk if col_chunk and col_chunk > 0 else n
@@ -403,117 +462,34 @@ def siglip_bwd(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
             f"batch {b} too large for the 32-bit g-slab addressing even at "
             f"the 256-column slab floor; shard the batch")
 
-    go = grad_output.detach().reshape(()).to(device=dev, dtype=torch.float32)
-    scale = go * t_true   # gradient GEMMs run against the original bf16
+    def slabs(c):
+        return (torch.empty((b, c), device=dev, dtype=g_dtype),
+                torch.empty((c, b), device=dev, dtype=g_dtype)
+                if fp8g else None)
 
-    # fp8 gradient GEMMs (hipBLASLt via torch._scaled_mm, measured 2.6× the
-    # bf16 matmul): the kernel's g slab is e4m3 at a fixed ×448 scale, the
-    # quantized embeddings carry per-tensor scales — all folded into
-    # _scaled_mm's scale args so no extra elementwise passes run.  Shapes
-    # must be 16-aligned; otherwise dequantize and use rocBLAS.
-    use_mm8 = (fp8g and b % 16 == 0 and n % 16 == 0
-               and d % 16 == 0 and hasattr(torch, "_scaled_mm"))
-    if fp8g and b % 4 != 0:   # packed gt stores need b%4
-        raise RuntimeError(f"{quant} backward requires batch % 4 == 0")
+    def band(j0, j1, g, gt):
+        _launch_tile(1, quant, zi_k, zt_k[j0:j1], tp_k, bp, scal, g=g, gt=gt,
+                     diag_offset=(None if diag_offset is None
+                                  else int(diag_offset) - j0))
+        return GBand(g, gt, ztxt[j0:j1], qc and qc.text_rows(j0, j1))
 
-    _one = torch.ones((), device=dev)
-
-    def mm8(a8, b8_rowmajor, s_ab):
-        """a8 (m, k) @ b8 (k, d) → bf16; mat2 re-laid column-major as
-        _scaled_mm requires (k ≤ a few thousand rows — cheap copy)."""
-        b_cm = b8_rowmajor.t().contiguous().t()   # column-major (k, d)
-        return torch._scaled_mm(a8, b_cm, scale_a=s_ab, scale_b=_one,
-                                out_dtype=torch.bfloat16)
-
-    def run_g(j0, j1, g_slab, diag, gt_slab=None):
-        zt_slab = zt_k[j0:j1]
-        if fp8g:
-            extra = ((None, None, None, None) if quant == "fp8" else ())
-            _check(g_fn(
-                ctypes.c_void_p(stream),
-                ctypes.c_void_p(zi_k.data_ptr()),
-                ctypes.c_void_p(zt_slab.data_ptr()),
-                ctypes.c_void_p(tp_k.data_ptr()),
-                ctypes.c_void_p(bp.data_ptr()),
-                ctypes.c_void_p(g_slab.data_ptr()),
-                ctypes.c_void_p(gt_slab.data_ptr()),
-                ctypes.c_void_p(scal.data_ptr()),
-                b, j1 - j0, d, diag, _kernel_flags(), *extra),
-                "siglip_bwd_g_fp8/mixed")
-        else:
-            _check(g_fn(
-                ctypes.c_void_p(stream),
-                ctypes.c_void_p(zi_k.data_ptr()),
-                ctypes.c_void_p(zt_slab.data_ptr()),
-                ctypes.c_void_p(tp_k.data_ptr()),
-                ctypes.c_void_p(bp.data_ptr()),
-                ctypes.c_void_p(g_slab.data_ptr()),
-                ctypes.c_void_p(scal.data_ptr()),
-                b, j1 - j0, d, diag, _kernel_flags()),
-                "siglip_bwd_g_bf16")
-
-    if step >= n:
-        # Single-slab fast path: no fp32 accumulation round trips.  dztxt is
-        # produced FIRST so the caller's on_dztxt hook (e.g. an async RCCL
-        # reduce-scatter) overlaps with the dzimg GEMM below.
-        g = torch.empty((b, n), device=dev, dtype=g_dtype)
-        gt = (torch.empty((n, b), device=dev, dtype=g_dtype)
-              if fp8g else None)
-        run_g(0, n, g, _DIAG_NONE if diag_offset is None else int(diag_offset),
-              gt)
-        if use_mm8:
-            s_t = ((scale / 448.0) * st).reshape(())
-            s_i = ((scale / 448.0) * si).reshape(())
-            dztxt = mm8(gt, zi_g, s_i)
-            if on_dztxt is not None:
-                on_dztxt(dztxt)
-            dzimg = mm8(g, zt_g, s_t)
-        else:
-            if fp8g:
-                g = g.to(torch.bfloat16) * (1.0 / 448.0)
-            dztxt = ((g.T @ zimg) * scale).to(ztxt.dtype)
-            if on_dztxt is not None:
-                on_dztxt(dztxt)
-            dzimg = (g @ ztxt) * scale
-    else:
-        dzimg_acc = torch.zeros((b, d), device=dev, dtype=torch.float32)
-        dztxt = torch.empty((n, d), device=dev, dtype=torch.bfloat16)
-        g_buf = torch.empty((b, step), device=dev, dtype=g_dtype)
-        gt_buf = (torch.empty((step, b), device=dev, dtype=g_dtype)
-                  if fp8g else None)
+    def chunks():
+        # One reused workspace pair: grad_gemms consumes each band before
+        # asking for the next, so the stream orders kernel after GEMMs.
+        bufs = slabs(step)
         for j0 in range(0, n, step):
             j1 = min(j0 + step, n)
-            c = j1 - j0
-            g = g_buf if c == step else torch.empty(
-                (b, c), device=dev, dtype=g_dtype)
-            gt = None
-            if fp8g:
-                gt = gt_buf if c == step else torch.empty(
-                    (c, b), device=dev, dtype=g_dtype)
-            diag = _DIAG_NONE if diag_offset is None else int(diag_offset) - j0
-            run_g(j0, j1, g, diag, gt)
-            if use_mm8 and c % 16 == 0:
-                s_t = ((scale / 448.0) * st).reshape(())
-                s_i = ((scale / 448.0) * si).reshape(())
-                dzimg_acc += mm8(g, zt_g[j0:j1], s_t).float()
-                dztxt[j0:j1] = mm8(gt, zi_g, s_i)
-            else:
-                g16 = (g.to(torch.bfloat16) * (1.0 / 448.0)
-                       ) if fp8g else g
-                # scale applied per chunk so mixed mm8/fallback chunks agree
-                dzimg_acc += ((g16 @ ztxt[j0:j1]) * scale).float()
-                dztxt[j0:j1] = (g16.T @ zimg) * scale
-        if on_dztxt is not None:
-            on_dztxt(dztxt)
-        dzimg = dzimg_acc
+            yield band(j0, j1, *(bufs if j1 - j0 == step else slabs(j1 - j0)))
 
-    dzimg = dzimg.to(zimg.dtype)
-    dztxt = dztxt.to(ztxt.dtype)
-    # dt' = go · Σ g·(z−bias) = go · t_eff · Σ g·dot_q  (t_eff ≡ t for bf16).
-    t_eff = tp_k.exp()
-    sv = reduce_out3(scal)
-    dt_prime = (sv[1] * go * t_eff).to(t_prime.dtype).reshape(t_prime.shape)
-    dbias = (sv[2] * go).to(bias.dtype).reshape(bias.shape)
+    go = grad_output.detach().reshape(()).to(device=dev, dtype=torch.float32)
+    # Single slab: no fp32 accumulation round trips.  bf16_scale=False: the
+    # recompute path multiplies by the fp32 scale, then casts.
+    dzimg, dztxt = grad_gemms(
+        band(0, n, *slabs(n)) if step >= n else chunks(), zimg, n,
+        go * tp.exp(), on_dztxt=on_dztxt, bf16_scale=False)
+    # t_eff ≡ t for bf16/mixed; for fp8 the kernel's dot is of quantized rows.
+    dt_prime, dbias = scalar_grads(reduce_out3(scal), go, tp_k.exp(),
+                                   t_prime, bias)
     return dzimg, dztxt, dt_prime, dbias
 
 
@@ -590,6 +566,115 @@ def scaled_mm8(a8: torch.Tensor, b8_rowmajor: torch.Tensor,
                             out_dtype=torch.bfloat16)
 
 
+def _mm8_ok(b: int, d: int, *cols: int) -> bool:
+    """Can the fp8 gradient GEMMs run on hipBLASLt (measured 2.6× the bf16
+    matmul)?  Every GEMM dimension must be 16-aligned; otherwise the e4m3
+    slabs are dequantized and rocBLAS runs in bf16."""
+    return (all(x % 16 == 0 for x in (b, d) + cols)
+            and hasattr(torch, "_scaled_mm"))
+
+
+class GBand(NamedTuple):
+    """One column band of dL/dlogit for :func:`grad_gemms`: the ``(b, c)``
+    slab (bf16, or e4m3 ×448), its ``(c, b)`` transpose (e4m3 only), the
+    ``c`` text rows it covers and the quantization of those rows."""
+    g: torch.Tensor
+    gt: Optional[torch.Tensor]
+    zt: torch.Tensor
+    qc: Optional[QuantCache] = None
+
+
+def grad_gemms(bands, zimg: torch.Tensor, n: int, scale: torch.Tensor,
+               on_dztxt=None, gt_full: Optional[torch.Tensor] = None,
+               bf16_scale: bool = False):
+    """The two gradient GEMMs of every backward regime → ``(dzimg, dztxt)``:
+    ``dztxt = scale·gᵀ@zimg`` FIRST, then ``on_dztxt(dztxt)`` (a distributed
+    caller's async reduce-scatter overlaps what follows), then
+    ``dzimg = scale·g@ztxt``.
+
+    ``bands`` is one :class:`GBand` covering all ``n`` text rows, or an
+    iterable of them in row order; an iterable may be lazy (each band is
+    consumed before the next is requested) and accumulates dzimg in fp32.
+    ``gt_full`` is the whole ``(n, b)`` e4m3 transpose when the image side
+    has one scale for all bands (the fp8 ring): dztxt is then one GEMM.
+
+    e4m3 slabs carry a fixed ×448; with the operands' per-tensor scales it
+    is folded into ``_scaled_mm``'s scale argument, so no elementwise pass
+    runs.  Unaligned shapes dequantize and use the bf16 matmul.
+
+    ``bf16_scale``: multiply bf16 products that STAY bf16 by the scale
+    rounded to bf16 (the saved-g paths: a fp32 0-d multiplier would promote
+    the whole product to fp32 — two extra full-tensor passes — and the
+    ~0.4% rounding is below the bf16 grad noise floor).  False (the
+    recompute path) multiplies by the fp32 scale and then casts.  Products
+    headed for the fp32 accumulator, and dequantized e4m3 slabs, always
+    take the fp32 scale.
+    """
+    b, d = zimg.shape
+    single = isinstance(bands, GBand)
+    s8 = scale / 448.0
+
+    def gemm(g, transpose, g8, other, other_q, s_q, c, keep_bf16):
+        """scale · op(g) @ other for a slab of ``c`` logit columns; ``g8`` is
+        op(g) as a row-major e4m3 tensor when the policy provides one."""
+        if g8 is not None and _mm8_ok(b, d, n, c):
+            return scaled_mm8(g8, other_q, s8 * s_q)
+        s = scale
+        if g8 is not None:
+            g = g.to(torch.bfloat16) * (1.0 / 448.0)
+        elif bf16_scale and keep_bf16:
+            s = scale.to(g.dtype)
+        return ((g.T if transpose else g) @ other) * s
+
+    def dztxt_of(band):
+        qc, c = band.qc, band.zt.shape[0]
+        return gemm(band.g, True, band.gt, zimg, qc and qc.zi_q,
+                    qc and qc.gemm_scales[0], c, True)
+
+    def dzimg_of(band):
+        qc, c = band.qc, band.zt.shape[0]
+        g8 = band.g if band.g.dtype == torch.float8_e4m3fn else None
+        return gemm(band.g, False, g8, band.zt, qc and qc.zt_q,
+                    qc and qc.gemm_scales[1], c, single)
+
+    if single:
+        dztxt = dztxt_of(bands).to(zimg.dtype)
+        if on_dztxt is not None:
+            on_dztxt(dztxt)
+        return dzimg_of(bands).to(zimg.dtype), dztxt
+
+    dzimg_acc = torch.zeros((b, d), device=zimg.device, dtype=torch.float32)
+    if gt_full is not None:
+        bands = list(bands)
+        qc = bands[0].qc
+        dztxt = gemm(gt_full, False, gt_full, zimg, qc.zi_q,
+                     qc.gemm_scales[0], n, True).to(zimg.dtype)
+        if on_dztxt is not None:
+            on_dztxt(dztxt)
+    else:
+        dztxt = torch.empty((n, d), device=zimg.device, dtype=zimg.dtype)
+    j0 = 0
+    for band in bands:
+        j1 = j0 + band.zt.shape[0]
+        if gt_full is None:
+            dztxt[j0:j1] = dztxt_of(band)
+        dzimg_acc += dzimg_of(band).float()
+        j0 = j1
+    if gt_full is None and on_dztxt is not None:
+        on_dztxt(dztxt)
+    return dzimg_acc.to(zimg.dtype), dztxt
+
+
+def scalar_grads(out3: torch.Tensor, go: torch.Tensor, t_eff: torch.Tensor,
+                 t_prime: torch.Tensor, bias: torch.Tensor):
+    """``(dt_prime, dbias)`` from a reduced ``[loss, Σg·dot, Σg]``:
+    dt' = go·t_eff·Σg·dot (chain rule through t = e^{t'}; t_eff carries the
+    per-tensor scales when the kernel's dot is of quantized rows),
+    dbias = go·Σg."""
+    return ((out3[1] * go * t_eff).to(t_prime.dtype).reshape(t_prime.shape),
+            (out3[2] * go).to(bias.dtype).reshape(bias.shape))
+
+
 def siglip_fwd_g(zimg: torch.Tensor, ztxt: torch.Tensor,
                  t_prime: torch.Tensor, bias: torch.Tensor,
                  diag_offset: Optional[int], quant: str = "bf16",
@@ -607,71 +692,31 @@ def siglip_fwd_g(zimg: torch.Tensor, ztxt: torch.Tensor,
     at column offset ``col0`` with the slab's width as row stride — the ring
     strategy assembles one ``(b, W·b)`` slab chunk by chunk.
     """
-    lib = _require_lib()
     _validate(zimg, ztxt, quant)
-    b, d = zimg.shape
-    n = ztxt.shape[0]
+    b, n = zimg.shape[0], ztxt.shape[0]
     dev = zimg.device
-    tp = _prep_scalar(t_prime, dev)
-    bp = _prep_scalar(bias, dev)
     fp8g = quant in ("fp8", "mixed")
     if fp8g and b % 4 != 0:
         raise RuntimeError(f"{quant} fwd+g requires batch % 4 == 0")
-    esz = 1 if fp8g else 2
     g_dtype = torch.float8_e4m3fn if fp8g else torch.bfloat16
+    # A supplied slab takes this chunk at columns (gᵀ: rows) col0:col0+n; a
+    # slab allocated here holds the chunk alone, whatever col0 says about
+    # the other one.
     if g_slab is None:
-        g_slab = torch.empty((b, n), device=dev, dtype=g_dtype)
-    ldg = g_slab.shape[1]
-    g_ptr = g_slab.data_ptr() + col0 * esz
-    gt_ptr = 0
-    if fp8g:
-        if gt_slab is None:
-            gt_slab = torch.empty((n, b), device=dev, dtype=g_dtype)
-        gt_ptr = gt_slab.data_ptr() + col0 * b * esz
-    if b * ldg * esz >= 2 ** 32:
-        raise RuntimeError(
-            "g slab exceeds the kernel's 32-bit addressing; use the "
-            "recompute path (save_g_enabled would have said no)")
+        g_slab = g = torch.empty((b, n), device=dev, dtype=g_dtype)
+    else:
+        g = g_slab[:, col0:col0 + n]
+    gt = None
+    if fp8g and gt_slab is None:
+        gt_slab = gt = torch.empty((n, b), device=dev, dtype=g_dtype)
+    elif fp8g:
+        gt = gt_slab[col0:col0 + n]
     if out3 is None:
         out3 = _out_buf(dev)
-    rs_extra = ()
-    if quant == "fp8":
-        if qcache is not None and len(qcache) == 8:
-            # row-wise: e8m0 scales feed the MFMA, ratios feed the slab
-            # folds; tp stays unmodified (acc is the true dot).
-            zi_q, zi_e8, zi_rat, _, zt_q, zt_e8, zt_rat, _ = qcache
-            tp_k = tp
-            rs_extra = (ctypes.c_void_p(zi_e8.data_ptr()),
-                        ctypes.c_void_p(zt_e8.data_ptr()),
-                        ctypes.c_void_p(zi_rat.data_ptr()),
-                        ctypes.c_void_p(zt_rat.data_ptr()))
-        else:
-            zi_q, si, zt_q, st = (qcache if qcache is not None
-                                  else quantize_fp8_pair(zimg, ztxt))
-            tp_k = tp + si.log() + st.log()
-            rs_extra = (None, None, None, None)
-        fn = lib.siglip_fwdg_fp8
-        zi_ptr, zt_ptr = zi_q.data_ptr(), zt_q.data_ptr()
-    else:
-        tp_k = tp
-        fn = lib.siglip_fwdg_mixed if quant == "mixed" else lib.siglip_fwdg_bf16
-        zi_ptr, zt_ptr = zimg.data_ptr(), ztxt.data_ptr()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
-    if fp8g:
-        rc = fn(ctypes.c_void_p(stream), ctypes.c_void_p(zi_ptr),
-                ctypes.c_void_p(zt_ptr), ctypes.c_void_p(tp_k.data_ptr()),
-                ctypes.c_void_p(bp.data_ptr()),
-                ctypes.c_void_p(out3.data_ptr()), ctypes.c_void_p(g_ptr),
-                ctypes.c_void_p(gt_ptr), b, n, d, ldg, diag, _kernel_flags(),
-                *rs_extra)
-    else:
-        rc = fn(ctypes.c_void_p(stream), ctypes.c_void_p(zi_ptr),
-                ctypes.c_void_p(zt_ptr), ctypes.c_void_p(tp_k.data_ptr()),
-                ctypes.c_void_p(bp.data_ptr()),
-                ctypes.c_void_p(out3.data_ptr()), ctypes.c_void_p(g_ptr),
-                b, n, d, ldg, diag, _kernel_flags())
-    _check(rc, "siglip_fwdg")
+    zi_k, zt_k, tp_k, rowscales = _logit_operands(
+        quant, zimg, ztxt, _prep_scalar(t_prime, dev), qcache)
+    _launch_tile(2, quant, zi_k, zt_k, tp_k, _prep_scalar(bias, dev), out3,
+                 g=g, gt=gt, diag_offset=diag_offset, rowscales=rowscales)
     return out3, g_slab, gt_slab if fp8g else None
 
 
@@ -734,49 +779,40 @@ def siglip_bwd_from_g(zimg: torch.Tensor, ztxt: torch.Tensor,
     """
     b, d = zimg.shape
     n = ztxt.shape[0]
-    dev = zimg.device
-    tp = _prep_scalar(t_prime, dev)
-    t_true = tp.exp()
-    go = grad_output.detach().reshape(()).to(device=dev, dtype=torch.float32)
-    scale = go * t_true
-    fp8g = quant in ("fp8", "mixed")
-    if fp8g and qcache is not None and len(qcache) == 8:
-        # row-wise policy: the slabs already fold the per-row ratios; the
-        # GEMM scale carries only the tensor-max factor, and dt' needs no
-        # scale correction (the MFMA accumulated the true dot).
-        zi_q, _, _, si_ref, zt_q, _, _, st_ref = qcache
-        dztxt = scaled_mm8(gt, zi_q, (scale / 448.0) * si_ref)
-        if on_dztxt is not None:
-            on_dztxt(dztxt)
-        dzimg = scaled_mm8(g, zt_q, (scale / 448.0) * st_ref)
-        t_eff = t_true
-    elif fp8g:
-        zi_q, si, zt_q, st = qcache
-        use_mm8 = (b % 16 == 0 and n % 16 == 0 and d % 16 == 0
-                   and hasattr(torch, "_scaled_mm"))
-        if use_mm8:
-            dztxt = scaled_mm8(gt, zi_q, (scale / 448.0) * si)
-            if on_dztxt is not None:
-                on_dztxt(dztxt)
-            dzimg = scaled_mm8(g, zt_q, (scale / 448.0) * st)
-        else:
-            g16 = g.to(torch.bfloat16) * (1.0 / 448.0)
-            dztxt = (g16.T @ zimg) * scale
-            if on_dztxt is not None:
-                on_dztxt(dztxt)
-            dzimg = (g16 @ ztxt) * scale
-        t_eff = t_true * si * st if quant == "fp8" else t_true
-    else:
-        # Scale in the GEMM output's own dtype: a fp32 0-d multiplier
-        # promotes the whole (n, d) product to fp32 (two extra full-tensor
-        # passes for the round trip); the bf16 scalar rounding (~0.4%) is
-        # below the bf16 grad noise floor.
-        scale_c = scale.to(g.dtype)
-        dztxt = (g.T @ zimg) * scale_c
-        if on_dztxt is not None:
-            on_dztxt(dztxt)
-        dzimg = (g @ ztxt) * scale_c
-        t_eff = t_true
-    dt_prime = (out3[1] * go * t_eff).to(t_prime.dtype).reshape(t_prime.shape)
-    dbias = (out3[2] * go).to(bias.dtype).reshape(bias.shape)
-    return (dzimg.to(zimg.dtype), dztxt.to(ztxt.dtype), dt_prime, dbias)
+    t_true = _prep_scalar(t_prime, zimg.device).exp()
+    go = grad_output.detach().reshape(()).to(device=zimg.device,
+                                             dtype=torch.float32)
+    qc = qcache if quant in ("fp8", "mixed") else None
+    t_eff = t_true
+    if qc is not None and qc.rowwise:
+        # The slabs already fold the per-row ratios, the GEMM scale carries
+        # only the tensor-max factor, and dt' needs no scale correction (the
+        # MFMA accumulated the true dot) — but there is no dequantize route.
+        if not _mm8_ok(b, d, n):
+            raise RuntimeError("row-wise fp8 needs 16-aligned GEMM shapes")
+    elif quant == "fp8":
+        t_eff = t_true * qc.si * qc.st
+    # bf16_scale=True: see grad_gemms — the saved-g path scales the bf16
+    # products in their own dtype.
+    dzimg, dztxt = grad_gemms(GBand(g, gt, ztxt, qc), zimg, n, go * t_true,
+                              on_dztxt=on_dztxt, bf16_scale=True)
+    return (dzimg, dztxt) + scalar_grads(out3, go, t_eff, t_prime, bias)
+
+
+def siglip_bwd_banded(zimg: torch.Tensor, ztxt: torch.Tensor,
+                      t_prime: torch.Tensor, bias: torch.Tensor,
+                      grad_output: torch.Tensor, out3: torch.Tensor,
+                      slabs, on_dztxt=None):
+    """Backward from column-banded saved g (bf16 ``(b, c_k)`` slabs covering
+    the text rows in order): per-band GEMMs, still no recompute.  Same
+    return contract as :func:`siglip_bwd_from_g`."""
+    t_true = _prep_scalar(t_prime, zimg.device).exp()
+    go = grad_output.detach().reshape(()).to(device=zimg.device,
+                                             dtype=torch.float32)
+    bands, j0 = [], 0
+    for g in slabs:
+        bands.append(GBand(g, None, ztxt[j0:j0 + g.shape[1]]))
+        j0 += g.shape[1]
+    dzimg, dztxt = grad_gemms(bands, zimg, ztxt.shape[0], go * t_true,
+                              on_dztxt=on_dztxt, bf16_scale=True)
+    return (dzimg, dztxt) + scalar_grads(out3, go, t_true, t_prime, bias)

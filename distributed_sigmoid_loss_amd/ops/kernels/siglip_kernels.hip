@@ -59,6 +59,12 @@
 //     column-major walk — temporally-close blocks share operand panels in
 //     the per-XCD L2 (measured best together: +4%).
 //
+// Host interface: every instantiation of the tile kernel is reached through
+// ONE exported function of fixed signature, siglip_tile(stream, mode, eb,
+// eb_g, ...), which validates its arguments and switches to launch<>; the
+// Python side (ops/__init__.py::_launch_tile) is its only caller.  The
+// l2norm_* and quant_fp8_* helpers keep one small export each.
+//
 // Requirements: bf16 d%8==0, fp8 d%16==0; b, n arbitrary (guarded path).
 // Compile: hipcc --offload-arch=gfx950 -O3 -shared -fPIC.
 
@@ -855,7 +861,7 @@ int launch(uintptr_t stream, const void* zimg, const void* ztxt,
 
 extern "C" {
 
-int siglip_ext_abi(void) { return 9; }
+int siglip_ext_abi(void) { return 10; }
 
 // Fused per-tensor fp8-e4m3 quantization: one amax pass (block reduce +
 // one atomicMax of the float bits per block — positive floats order as
@@ -1024,91 +1030,50 @@ int quant_fp8_bf16(uintptr_t stream, const void* x, void* q,
   return (int)hipGetLastError();
 }
 
-int siglip_fwd_bf16(uintptr_t stream, const void* zimg, const void* ztxt,
-                    const void* t_prime, const void* bias, void* loss_out,
-                    int b, int n, int d, int diag, int flags) {
-  return launch<0, 2>(stream, zimg, ztxt, t_prime, bias, loss_out, nullptr,
-                      nullptr, b, n, d, n, diag, flags);
-}
-
-int siglip_bwd_g_bf16(uintptr_t stream, const void* zimg, const void* ztxt,
-                      const void* t_prime, const void* bias, void* g_out,
-                      void* scal, int b, int n, int d, int diag, int flags) {
-  return launch<1, 2>(stream, zimg, ztxt, t_prime, bias, scal, g_out,
-                      nullptr, b, n, d, n, diag, flags);
-}
-
-// fp8 entry points: the trailing scale pointers select the policy —
-// null → per-tensor (scales folded into the temperature upstream);
-// non-null → row-wise e8m0 hardware dequant (a_e8/b_e8: per-row exponent
-// bytes; a_rat/b_rat: fp32 per-row scale ÷ tensor-max scale, consumed by
-// the slab folds in MODE 1/2).
-int siglip_fwd_fp8(uintptr_t stream, const void* zimg, const void* ztxt,
-                   const void* t_prime, const void* bias, void* loss_out,
-                   int b, int n, int d, int diag, int flags,
-                   const void* a_e8, const void* b_e8) {
-  return launch<0, 1>(stream, zimg, ztxt, t_prime, bias, loss_out, nullptr,
-                      nullptr, b, n, d, n, diag, flags, a_e8, b_e8);
-}
-
-// Mixed policy: bf16 logits recompute, e4m3 ×448 g and gᵀ slabs (for the
-// fp8 gradient GEMMs) — full-precision loss surface, compressed grads.
-int siglip_bwd_g_mixed(uintptr_t stream, const void* zimg, const void* ztxt,
-                       const void* t_prime, const void* bias, void* g_out,
-                       void* gt_out, void* scal, int b, int n, int d,
-                       int diag, int flags) {
-  if (b % 4 != 0) return (int)hipErrorInvalidValue;
-  return launch<1, 2, 1>(stream, zimg, ztxt, t_prime, bias, scal, g_out,
-                         gt_out, b, n, d, n, diag, flags);
-}
-
-// fp8 backward emits g (b,n) AND its transpose gt (n,b), both e4m3 ×448.
-int siglip_bwd_g_fp8(uintptr_t stream, const void* zimg, const void* ztxt,
-                     const void* t_prime, const void* bias, void* g_out,
-                     void* gt_out, void* scal, int b, int n, int d, int diag,
-                     int flags, const void* a_e8, const void* b_e8,
-                     const void* a_rat, const void* b_rat) {
-  if (b % 4 != 0) return (int)hipErrorInvalidValue;  // packed 4-B gt stores
-  return launch<1, 1>(stream, zimg, ztxt, t_prime, bias, scal, g_out,
-                      gt_out, b, n, d, n, diag, flags, a_e8, b_e8, a_rat,
-                      b_rat);
-}
-
-// ---- fwd+g ("saved-g") entry points: one kernel computes the loss, the g
-// slab and both scalar partials — backward then runs only the two gradient
-// GEMMs on the saved slab (no logits recompute).  `out` is a zeroed
-// float[8][32] per-XCD-slot buffer; slot layout {loss, Σg·dot, Σg} — the
-// caller sums slots.  `ldg` is the g-slab row stride in elements (≥ n) so
-// the ring strategy can write each chunk at its column offset inside one
-// (b, W·b) slab.
-
-int siglip_fwdg_bf16(uintptr_t stream, const void* zimg, const void* ztxt,
-                     const void* t_prime, const void* bias, void* out,
-                     void* g_out, int b, int n, int d, int ldg, int diag,
-                     int flags) {
-  return launch<2, 2>(stream, zimg, ztxt, t_prime, bias, out, g_out,
-                      nullptr, b, n, d, ldg, diag, flags);
-}
-
-// mixed: bf16 logits, e4m3 ×448 g and gᵀ slabs for the fp8 grad GEMMs.
-int siglip_fwdg_mixed(uintptr_t stream, const void* zimg, const void* ztxt,
-                      const void* t_prime, const void* bias, void* out,
-                      void* g_out, void* gt_out, int b, int n, int d,
-                      int ldg, int diag, int flags) {
-  if (b % 4 != 0) return (int)hipErrorInvalidValue;
-  return launch<2, 2, 1>(stream, zimg, ztxt, t_prime, bias, out, g_out,
-                         gt_out, b, n, d, ldg, diag, flags);
-}
-
-int siglip_fwdg_fp8(uintptr_t stream, const void* zimg, const void* ztxt,
-                    const void* t_prime, const void* bias, void* out,
-                    void* g_out, void* gt_out, int b, int n, int d,
-                    int ldg, int diag, int flags, const void* a_e8,
-                    const void* b_e8, const void* a_rat, const void* b_rat) {
-  if (b % 4 != 0) return (int)hipErrorInvalidValue;
-  return launch<2, 1>(stream, zimg, ztxt, t_prime, bias, out, g_out,
-                      gt_out, b, n, d, ldg, diag, flags, a_e8, b_e8, a_rat,
-                      b_rat);
+// The single tile-kernel entry point.  (mode, eb, eb_g) selects one of the
+// eight instantiated combinations of tile_body's template parameters:
+//   mode  0 = fwd (loss only), 1 = bwd-g (recompute: g slab + scalar
+//         partials), 2 = fwd+g ("saved-g": loss, g slab and both partials in
+//         one pass, so backward is pure GEMMs);
+//   eb    logit operand bytes: 2 = bf16, 1 = e4m3;
+//   eb_g  g-slab element bytes: 2 = bf16 g only, 1 = e4m3 x448 g AND its
+//         transpose gt (n, b) for the fp8 gradient GEMMs.
+//         (eb, eb_g) = (2, 1) is the "mixed" policy.
+// `out` is a zeroed float[8][32] per-XCD-slot buffer, slot layout
+// {loss, sum g*dot, sum g}; the caller sums slots.  `ldg` is the g-slab row
+// stride in elements (>= n), so the ring strategy can write each chunk at
+// its column offset inside one (b, W*b) slab.  The four row-scale pointers
+// select the fp8 policy: null = per-tensor (scales folded into the
+// temperature upstream); non-null = row-wise e8m0 hardware dequant
+// (a_e8/b_e8: per-row exponent bytes; a_rat/b_rat: fp32 per-row scale /
+// tensor-max scale, consumed by the slab folds in modes 1/2).
+int siglip_tile(uintptr_t stream, int mode, int eb, int eb_g,
+                const void* zimg, const void* ztxt, const void* t_prime,
+                const void* bias, void* out, void* g_out, void* gt_out,
+                const void* a_e8, const void* b_e8, const void* a_rat,
+                const void* b_rat, int b, int n, int d, int ldg, int diag,
+                int flags) {
+  // Argument checks, before any HIP call.  The g-emitting modes need their
+  // slabs; the e4m3 slab pair additionally needs b % 4 (packed 4-B gt
+  // stores).  Mode 0 writes no slab, so (0, 1, 1) takes any b.
+  if (mode != 0 && g_out == nullptr) return (int)hipErrorInvalidValue;
+  if (mode != 0 && eb_g == 1 && (gt_out == nullptr || b % 4 != 0))
+    return (int)hipErrorInvalidValue;
+#define SIGLIP_TILE_CASE(M, EB, EB_G)                                       \
+  if (mode == M && eb == EB && eb_g == EB_G)                                \
+    return launch<M, EB, EB_G>(stream, zimg, ztxt, t_prime, bias, out,      \
+                               g_out, gt_out, b, n, d, ldg, diag, flags,    \
+                               a_e8, b_e8, a_rat, b_rat)
+  SIGLIP_TILE_CASE(0, 2, 2);
+  SIGLIP_TILE_CASE(1, 2, 2);
+  SIGLIP_TILE_CASE(0, 1, 1);
+  SIGLIP_TILE_CASE(1, 2, 1);
+  SIGLIP_TILE_CASE(1, 1, 1);
+  SIGLIP_TILE_CASE(2, 2, 2);
+  SIGLIP_TILE_CASE(2, 2, 1);
+  SIGLIP_TILE_CASE(2, 1, 1);
+#undef SIGLIP_TILE_CASE
+  return (int)hipErrorInvalidValue;
 }
 
 }  // extern "C"

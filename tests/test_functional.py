@@ -2,6 +2,7 @@
 materialized-label formula, plus the manual backward used by the fused
 distributed Function."""
 
+import dataclasses
 import math
 
 import pytest
@@ -102,6 +103,51 @@ def test_chunk_fwd_bwd_helpers_consistent():
     g2 = chunk_loss_bwd(zi, zt, tp, bs, 2, torch.tensor(1.0), col_chunk=3)
     for a, b_ in zip(g1, g2):
         assert torch.allclose(a, b_, rtol=1e-6, atol=1e-7)
+
+
+def test_chunk_helpers_ignore_qcache_on_torch_path():
+    """qcache= is forwarded to the HIP ops only; the torch path returns the
+    same values with and without the argument."""
+    zi, zt, tp, bs = rand_inputs(6, 10, 8, seed=4)
+    go = torch.tensor(0.5)
+    assert torch.equal(
+        chunk_loss_fwd(zi, zt, tp, bs, diag_offset=2, qcache=None),
+        chunk_loss_fwd(zi, zt, tp, bs, diag_offset=2))
+    with_q = chunk_loss_bwd(zi, zt, tp, bs, 2, go, col_chunk=3, qcache=None)
+    without = chunk_loss_bwd(zi, zt, tp, bs, 2, go, col_chunk=3)
+    for a, b_ in zip(with_q, without):
+        assert torch.equal(a, b_)
+
+
+@pytest.mark.parametrize("rowwise", [False, True])
+def test_quant_cache_round_trip(rowwise):
+    """QuantCache flattens to tensors (save_for_backward) and rebuilds
+    field for field, for both policies."""
+    from distributed_sigmoid_loss_amd.ops import QuantCache
+    g = torch.Generator().manual_seed(5)
+    zi_q, zt_q = torch.randn(4, 16, generator=g), torch.randn(6, 16,
+                                                              generator=g)
+    if rowwise:
+        c = QuantCache(
+            zi_q, zt_q,
+            zi_e8=torch.randint(0, 255, (4,), generator=g).to(torch.uint8),
+            zt_e8=torch.randint(0, 255, (6,), generator=g).to(torch.uint8),
+            zi_ratio=torch.rand(4, generator=g),
+            zt_ratio=torch.rand(6, generator=g),
+            si_ref=torch.tensor(0.25), st_ref=torch.tensor(0.5))
+    else:
+        c = QuantCache(zi_q, zt_q, torch.tensor(0.01), torch.tensor(0.02))
+    assert c.rowwise is rowwise
+    ts = c.tensors()
+    assert len(ts) == (8 if rowwise else 4)
+    assert all(isinstance(t, torch.Tensor) for t in ts)
+    r = QuantCache.from_tensors(ts)
+    assert r.rowwise is rowwise
+    for f in dataclasses.fields(QuantCache):
+        a, b_ = getattr(c, f.name), getattr(r, f.name)
+        assert (a is None and b_ is None) or (a is b_), f.name
+    with pytest.raises(ValueError):
+        QuantCache.from_tensors(ts[:3])
 
 
 def test_shape_validation():

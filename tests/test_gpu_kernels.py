@@ -173,6 +173,42 @@ def test_extension_is_intree_so():
         assert any("_siglip_hip.so" in line for line in f)
 
 
+def test_siglip_tile_rejects_bad_arguments():
+    """The single C entry point returns non-zero, without launching, for an
+    un-instantiated (mode, eb, eb_g), for e4m3 slabs with b % 4 != 0, and
+    for a g-emitting mode without a g slab.  Every buffer is real and sized
+    for the largest call, whatever the arguments claim."""
+    import ctypes
+    lib = ops._require_lib()
+    b, n, d = 8, 256, 128
+    zi = torch.zeros((b, d), device="cuda", dtype=torch.bfloat16)
+    zt = torch.zeros((n, d), device="cuda", dtype=torch.bfloat16)
+    tp = torch.zeros((), device="cuda")
+    bs = torch.zeros((), device="cuda")
+    out = ops._out_buf("cuda")
+    g = torch.zeros((b, n), device="cuda", dtype=torch.bfloat16)
+    gt = torch.zeros((n, b), device="cuda", dtype=torch.uint8)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(mode, eb, eb_g, b=b, g=g):
+        p = [ctypes.c_void_p(t.data_ptr()) for t in (zi, zt, tp, bs, out)]
+        p += [None if g is None else ctypes.c_void_p(g.data_ptr()),
+              ctypes.c_void_p(gt.data_ptr())]
+        return lib.siglip_tile(ctypes.c_void_p(stream), mode, eb, eb_g, *p,
+                               None, None, None, None, b, n, d, n,
+                               ops._DIAG_NONE, 0)
+
+    assert call(0, 1, 2) != 0            # not an instantiated combination
+    assert call(2, 1, 1, b=6) != 0       # packed gt stores need b % 4
+    assert call(2, 2, 2, g=None) != 0    # mode 2 writes a g slab
+    torch.cuda.synchronize()
+    assert not out.any() and not g.any() and not gt.any()
+    # the same call with sound arguments launches and writes the loss
+    assert call(0, 2, 2) == 0
+    torch.cuda.synchronize()
+    assert out[:, 0].sum().item() > 0
+
+
 @pytest.mark.parametrize("b,d", [(256, 768), (1000, 66), (8, 2)])
 def test_fused_l2_normalize(b, d):
     """Fused single-pass normalize kernels vs F.normalize autograd chain."""

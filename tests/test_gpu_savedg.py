@@ -226,7 +226,8 @@ def test_rowwise_quant_keeps_per_row_precision():
     q_r, e8, ratio, s_ref = ops._quant_fp8_rowwise(x)
     # reconstruct: q · 2^(e8-127) per row
     rec_r = q_r.float() * torch.exp2(e8.float() - 127.0).unsqueeze(1)
-    q_t, s_t = ops.quantize_fp8_pair(x, x)[:2]
+    qc_t = ops.quantize_fp8_pair(x, x)
+    q_t, s_t = qc_t.zi_q, qc_t.si
     rec_t = q_t.float() * s_t
     torch.cuda.synchronize()
 
@@ -274,10 +275,10 @@ def test_fp8_wire_simulated_roundtrip_gpu():
     assert torch.equal(rq, zt_q) and torch.equal(rs, st.reshape(()))
 
     direct = ops.siglip_fwd_g(zi, zt, tp, bs, None, quant="fp8",
-                              qcache=(zi_q, si, zt_q, st))
+                              qcache=ops.QuantCache(zi_q, zt_q, si, st))
     via_wire = ops.siglip_fwd_g(zi, (rq.to(torch.float32) * rs).to(zt.dtype),
                                 tp, bs, None, quant="fp8",
-                                qcache=(zi_q, si, rq, rs))
+                                qcache=ops.QuantCache(zi_q, rq, si, rs))
     torch.cuda.synchronize()
     assert torch.equal(ops.reduce_out3(direct[0]), ops.reduce_out3(via_wire[0]))
     assert torch.equal(direct[1], via_wire[1])          # g slabs bitwise
@@ -309,6 +310,73 @@ def test_banded_savedg_matches_recompute():
                 os.environ.pop(k, None)
     for a, b_ in zip(outs["banded"], outs["recompute"]):
         assert torch.allclose(a.float(), b_.float(), rtol=2e-2, atol=1e-3), \
+            (a.float() - b_.float()).abs().max()
+
+
+@pytest.mark.parametrize("n", [768, 700])
+def test_banded_grads_three_bands(n):
+    """The banded backward through ops.grad_gemms at three 256-column bands
+    — last one full (768) and ragged (700, 188 columns) — against the
+    recompute path, at test_banded_savedg_matches_recompute's tolerances."""
+    b, d = 512, 256
+    outs = {}
+    for mode, env in (("banded", {"SIGLIP_SAVE_G_MAX_BYTES": "1000",
+                                  "SIGLIP_BANDED_STEP": "256"}),
+                      ("recompute", {"SIGLIP_SAVE_G": "0"})):
+        for k, v in env.items():
+            os.environ[k] = v
+        try:
+            zi, zt, tp, bs = make_inputs(b, n, d, seed=78)
+            zi = zi.clone().requires_grad_(True)
+            zt = zt.clone().requires_grad_(True)
+            tp = tp.clone().requires_grad_(True)
+            bs = bs.clone().requires_grad_(True)
+            loss = sigmoid_contrastive_loss(zi, zt, tp, bs, diag_offset=100)
+            loss.backward()
+            torch.cuda.synchronize()
+            outs[mode] = (loss.detach(), zi.grad, zt.grad, tp.grad, bs.grad)
+        finally:
+            for k in env:
+                os.environ.pop(k, None)
+    for a, b_ in zip(outs["banded"], outs["recompute"]):
+        assert torch.allclose(a.float(), b_.float(), rtol=2e-2, atol=1e-3), \
+            (a.float() - b_.float()).abs().max()
+
+
+@pytest.mark.parametrize("b", [256, 260])   # interior tiles / ragged edge
+def test_fp8_ring_recompute_single_gpu(b):
+    """The ring Function's fp8 RECOMPUTE backward (SIGLIP_SAVE_G=0), which
+    hands each chunk's forward quantization to chunk_loss_bwd, at W=1
+    against the plain fused loss under the same env: the same kernels on the
+    same quantized inputs, at the fp8 saved-g-vs-recompute bound."""
+    from distributed_sigmoid_loss_amd.losses.sigmoid_loss import (
+        _RingAllGatherLoss)
+    d = 128
+    results = {}
+    os.environ["SIGLIP_SAVE_G"] = "0"
+    try:
+        for mode in ("ring", "plain"):
+            zi, zt, tp, bs = make_inputs(b, b, d, seed=21)
+            zi = zi.clone().requires_grad_(True)
+            zt = zt.clone().requires_grad_(True)
+            tp = tp.clone().requires_grad_(True)
+            bs = bs.clone().requires_grad_(True)
+            if mode == "ring":
+                # (group, col_chunk, impl, quant, want_grad, bidir); no
+                # process group, so W=1
+                loss = _RingAllGatherLoss.apply(zi, zt, tp, bs, None, None,
+                                                "auto", "fp8", True, False)
+            else:
+                loss = sigmoid_contrastive_loss(zi, zt, tp, bs,
+                                                diag_offset=0, quant="fp8")
+            loss.backward()
+            torch.cuda.synchronize()
+            results[mode] = (loss.detach(), zi.grad, zt.grad, tp.grad,
+                             bs.grad)
+    finally:
+        os.environ.pop("SIGLIP_SAVE_G", None)
+    for a, b_ in zip(results["ring"], results["plain"]):
+        assert torch.allclose(a.float(), b_.float(), rtol=5e-2, atol=5e-3), \
             (a.float() - b_.float()).abs().max()
 
 

@@ -9,7 +9,6 @@ gradient GEMMs, encoder fwd/bwd, optimizer.  Run on a GPU box:
 from __future__ import annotations
 
 import argparse
-import ctypes
 import os
 import sys
 
@@ -76,20 +75,14 @@ def main():
           f"{2.0 * b * ref_n * d / t_ref / 1e9:7.1f} TF/s  (n={ref_n})")
 
     # bwd pieces: g-kernel alone, then GEMMs alone.
-    lib = ops._require_lib()
     c = min(args.col_chunk, b)
     g = torch.empty((b, c), device=dev, dtype=torch.bfloat16)
     scal = ops._out_buf(dev)
     ztc = zt[:c].contiguous()
-    stream = torch.cuda.current_stream().cuda_stream
 
     def g_kernel():
-        ops._check(lib.siglip_bwd_g_bf16(
-            ctypes.c_void_p(stream),
-            ctypes.c_void_p(zi.data_ptr()), ctypes.c_void_p(ztc.data_ptr()),
-            ctypes.c_void_p(tp.data_ptr()), ctypes.c_void_p(bs.data_ptr()),
-            ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(scal.data_ptr()),
-            b, c, d, 0, ops._kernel_flags()), "bwd_g")
+        ops._launch_tile(1, "bf16", zi, ztc, tp, bs, scal, g=g,
+                         diag_offset=0)
 
     t_g = time_fn(g_kernel)
     nchunks = (b + c - 1) // c

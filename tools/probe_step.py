@@ -94,8 +94,8 @@ def main():
                                         quant="fp8", qcache=qc)
         out3 = ops.reduce_out3(buf)
         sc = torch.tensor(0.005, device=dev)
-        t_m1 = time_fn(lambda: ops.scaled_mm8(gt8, qc[0], sc))
-        t_m2 = time_fn(lambda: ops.scaled_mm8(g8, qc[2], sc))
+        t_m1 = time_fn(lambda: ops.scaled_mm8(gt8, qc.zi_q, sc))
+        t_m2 = time_fn(lambda: ops.scaled_mm8(g8, qc.zt_q, sc))
         print(f"fp8 GEMM gt8@zi_q     : {t_m1:7.3f} ms")
         print(f"fp8 GEMM g8@zt_q      : {t_m2:7.3f} ms")
         go = torch.tensor(1.0, device=dev)

@@ -42,7 +42,13 @@ class ProjectionTower(nn.Module):
         self.proj = nn.Linear(in_dim, emb_dim, bias=False)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        from ..ops import l2_normalize
+        from ..ops import l2_normalize, linear_nobias
+        # ``proj`` stays an nn.Linear (parameter names, state_dict and DDP
+        # hooks unchanged); on the bf16 GPU path its weight gradient — a
+        # 768×768 output over a 32k-deep reduction — comes from the split-K
+        # HIP kernel instead of the library's 24-workgroup GEMM.
+        if x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16:
+            return l2_normalize(linear_nobias(x, self.proj.weight))
         return l2_normalize(self.proj(x))
 
 

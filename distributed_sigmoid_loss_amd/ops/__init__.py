@@ -19,6 +19,10 @@ exposes:
   logits, fp8 gradient GEMMs).
 - fused tower helpers: :func:`l2_normalize` (single-pass fwd/bwd) and the
   fused fp8 quantizers.
+- tower backward: :func:`linear_wgrad` (split-K ``dyᵀ @ x`` with a
+  deterministic two-stage reduction), wired into the projection towers by
+  :func:`linear_nobias`; :func:`scale_bf16_` (in-place vectorized scale of
+  the saved-g gradient products).
 
 Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
@@ -137,9 +141,9 @@ def _load():
         _lib_err = f"failed to load {SO_PATH}: {e}"
         return None
     lib.siglip_ext_abi.restype = ctypes.c_int
-    if lib.siglip_ext_abi() != 10:
+    if lib.siglip_ext_abi() != 11:
         _lib_err = (f"stale HIP extension at {SO_PATH} "
-                    f"(ABI {lib.siglip_ext_abi()}, need 10); rebuild with: "
+                    f"(ABI {lib.siglip_ext_abi()}, need 11); rebuild with: "
                     "python -m distributed_sigmoid_loss_amd.ops.build --force")
         return None
     # (stream, mode, eb, eb_g, 11 pointers, b, n, d, ldg, diag, flags)
@@ -157,6 +161,16 @@ def _load():
     lib.quant_fp8_rowwise_bf16.restype = ctypes.c_int
     lib.quant_fp8_rowwise_bf16.argtypes = (
         [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2)
+    lib.linear_wgrad_plan.restype = ctypes.c_int
+    lib.linear_wgrad_plan.argtypes = [ctypes.c_int] * 4
+    # (stream, a, x, ws, dw, K, M, N, lda, ldx, slices)
+    lib.linear_wgrad_bf16.restype = ctypes.c_int
+    lib.linear_wgrad_bf16.argtypes = (
+        [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3
+        + [ctypes.c_longlong] * 2 + [ctypes.c_int])
+    lib.scale_bf16_inplace.restype = ctypes.c_int
+    lib.scale_bf16_inplace.argtypes = (
+        [ctypes.c_void_p] * 3 + [ctypes.c_longlong])
     _lib = lib
     return _lib
 
@@ -574,6 +588,129 @@ def _mm8_ok(b: int, d: int, *cols: int) -> bool:
             and hasattr(torch, "_scaled_mm"))
 
 
+def _scale_inplace_ok(x: torch.Tensor) -> bool:
+    return (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
+            and x.data_ptr() % 16 == 0 and extension_available())
+
+
+def scale_bf16_(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """In-place ``x *= scale.to(bf16)`` for a contiguous bf16 GPU tensor and a
+    0-d device scalar, by the vectorized HIP kernel (16-byte accesses; fp32
+    product of the element and the bf16-rounded scale, rounded to
+    nearest-even — bitwise what ``x * scale.to(torch.bfloat16)`` gives).
+    Returns ``x``."""
+    lib = _require_lib()
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()):
+        raise RuntimeError("scale_bf16_ needs a contiguous bf16 GPU tensor")
+    s = scale.detach().reshape(()).to(device=x.device, dtype=torch.float32)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    _check(lib.scale_bf16_inplace(
+        ctypes.c_void_p(stream), ctypes.c_void_p(x.data_ptr()),
+        ctypes.c_void_p(s.data_ptr()), ctypes.c_longlong(x.numel())),
+        "scale_bf16_inplace")
+    return x
+
+
+def _rows_16b(t: torch.Tensor) -> torch.Tensor:
+    """``t`` itself when the wgrad kernel can read it in place (unit column
+    stride, 16-byte-aligned rows), otherwise its contiguous copy."""
+    if (t.stride(1) == 1 and t.stride(0) >= t.shape[1]
+            and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0):
+        return t
+    return t.contiguous()
+
+
+def _wgrad_slices(k: int, m: int, n: int, device) -> int:
+    """K-slice count for the split-K weight-gradient kernel (0: unsupported
+    dims).  SIGLIP_WGRAD_SLICES overrides the plan, for sweeps."""
+    n_cu = torch.cuda.get_device_properties(device).multi_processor_count
+    s = _require_lib().linear_wgrad_plan(k, m, n, n_cu)
+    env = os.environ.get("SIGLIP_WGRAD_SLICES")
+    return int(env) if s and env else s
+
+
+def linear_wgrad_supported(dy: torch.Tensor, x: torch.Tensor) -> bool:
+    """Does the native split-K kernel take this ``dyᵀ @ x``?  GPU, bf16, 2-D,
+    a shared non-empty batch, and M, N multiples of 8 (its 16-byte loads)."""
+    return (dy.is_cuda and x.is_cuda and dy.dtype == torch.bfloat16
+            and x.dtype == torch.bfloat16 and dy.dim() == 2 and x.dim() == 2
+            and dy.shape[0] == x.shape[0] and dy.shape[0] > 0
+            and dy.shape[1] > 0 and x.shape[1] > 0
+            and dy.shape[1] % 8 == 0 and x.shape[1] % 8 == 0
+            and extension_available())
+
+
+def linear_wgrad(dy: torch.Tensor, x: torch.Tensor,
+                 slices: Optional[int] = None) -> torch.Tensor:
+    """Weight gradient of a bias-free linear layer: ``dW (M, N) = dyᵀ @ x``
+    for ``dy`` (B, M) and ``x`` (B, N).
+
+    bf16 GPU operands run the split-K HIP kernel: (output tiles) × (K slices)
+    workgroups fill the chip where the library's output-tiled GEMM occupies
+    24 of 256 CUs at 768×768; slices leave fp32 partials in a workspace from
+    the torch allocator and a second kernel sums them in slice order — no
+    atomics, bitwise reproducible.  ``dy`` / ``x`` may be row-strided views.
+    Dims the kernel does not take fall back to the library matmul."""
+    if not linear_wgrad_supported(dy, x):
+        if dy.is_cuda and dy.dtype == torch.bfloat16:
+            _require_lib()      # a missing extension is an error, not a path
+        return dy.t() @ x
+    lib = _require_lib()
+    dy, x = _rows_16b(dy.detach()), _rows_16b(x.detach())
+    k, m = dy.shape
+    n = x.shape[1]
+    if slices is None:
+        slices = _wgrad_slices(k, m, n, dy.device)
+    dw = torch.empty((m, n), device=dy.device, dtype=torch.bfloat16)
+    ws = torch.empty((max(slices, 1), m, n), device=dy.device,
+                     dtype=torch.float32)
+    stream = torch.cuda.current_stream(dy.device).cuda_stream
+    _check(lib.linear_wgrad_bf16(
+        ctypes.c_void_p(stream), ctypes.c_void_p(dy.data_ptr()),
+        ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+        ctypes.c_void_p(dw.data_ptr()), k, m, n, dy.stride(0), x.stride(0),
+        slices), "linear_wgrad_bf16")
+    return dw
+
+
+def native_wgrad_enabled() -> bool:
+    """SIGLIP_NATIVE_WGRAD=0 sends the towers' weight gradient back to the
+    library GEMM (A/B runs); default on."""
+    return os.environ.get("SIGLIP_NATIVE_WGRAD", "1") != "0"
+
+
+class _LinearNativeWgrad(torch.autograd.Function):
+    """Bias-free ``x @ Wᵀ`` whose weight gradient comes from
+    :func:`linear_wgrad`.  Forward and the input gradient (computed only when
+    asked for) stay on the library."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        return x @ weight.t()
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dx = dy @ weight if ctx.needs_input_grad[0] else None
+        dw = linear_wgrad(dy, x) if ctx.needs_input_grad[1] else None
+        return dx, dw
+
+
+def linear_nobias(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """``x @ weightᵀ``.  2-D bf16 GPU inputs with supported dims (and
+    SIGLIP_NATIVE_WGRAD unset or 1) take :class:`_LinearNativeWgrad`;
+    everything else is ``F.linear``."""
+    if (native_wgrad_enabled() and x.dim() == 2 and weight.dim() == 2
+            and x.is_cuda and weight.is_cuda
+            and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+            and x.shape[0] > 0 and weight.shape[0] % 8 == 0
+            and weight.shape[1] % 8 == 0 and extension_available()):
+        return _LinearNativeWgrad.apply(x, weight)
+    import torch.nn.functional as F
+    return F.linear(x, weight)
+
+
 class GBand(NamedTuple):
     """One column band of dL/dlogit for :func:`grad_gemms`: the ``(b, c)``
     slab (bf16, or e4m3 ×448), its ``(c, b)`` transpose (e4m3 only), the
@@ -623,7 +760,12 @@ def grad_gemms(bands, zimg: torch.Tensor, n: int, scale: torch.Tensor,
         if g8 is not None:
             g = g.to(torch.bfloat16) * (1.0 / 448.0)
         elif bf16_scale and keep_bf16:
-            s = scale.to(g.dtype)
+            out = (g.T if transpose else g) @ other
+            if _scale_inplace_ok(out):
+                # The product is fresh, so scale it in place: one vectorized
+                # pass, bit-identical to ``out * scale.to(bf16)``.
+                return scale_bf16_(out, scale)
+            return out * scale.to(g.dtype)
         return ((g.T if transpose else g) @ other) * s
 
     def dztxt_of(band):

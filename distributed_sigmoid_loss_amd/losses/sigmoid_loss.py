@@ -31,6 +31,7 @@ import torch
 import torch.nn as nn
 import torch.distributed as dist
 
+from .. import ops as _ops
 from .functional import (
     sigmoid_contrastive_loss,
     chunk_loss_fwd,
@@ -40,23 +41,9 @@ from ..parallel.collectives import all_gather_with_grad, _backend_is_gloo
 from ..parallel.ring import (
     neighbour_exchange_with_grad,
     neighbour_exchange_bidir_with_grad,
-    neighbour_exchange_start,
-    neighbour_exchange_bidir_start,
-    quantized_exchange_start,
-    quantized_exchange_bidir_start,
+    hop_span,
+    walk_ring,
 )
-from ..utils.profiling import roctx_range, HopStats
-
-
-import contextlib
-
-
-@contextlib.contextmanager
-def _hop_span(label):
-    # roctx marker for external profilers + CUDA-event pair for the
-    # in-process per-hop stats (SIGLIP_HOP_STATS=1 / bench --csv).
-    with roctx_range(label), HopStats.record(label):
-        yield
 
 
 def _world_and_rank(group=None):
@@ -65,18 +52,224 @@ def _world_and_rank(group=None):
     return 1, 0
 
 
+class _PlainWire:
+    """Ring wire format of the bf16 / mixed policies: the chunk itself."""
+
+    def pack(self, ztxt):
+        return (ztxt,)
+
+    def qcache(self, payload):
+        return None
+
+    def unpack(self, payload):
+        return payload[0], None
+
+
+class _Fp8Wire:
+    """Ring wire format of the fp8 policy: ``(e4m3 codes, (1,) fp32 scale)``.
+
+    Every shard is quantized ONCE, by its owner — half the xGMI bytes per hop
+    versus bf16, and every rank computes with the exact quantized values the
+    owner produced.  The image side is quantized once, here, and shared by
+    every chunk's :class:`ops.QuantCache`.
+    """
+
+    def __init__(self, zimg):
+        self.zi_q, self.si = _ops._quant_fp8(zimg)
+        self.dtype = zimg.dtype
+
+    def pack(self, ztxt):
+        zt_q, st = _ops._quant_fp8(ztxt)
+        return (zt_q, st.reshape(1).float())
+
+    def qcache(self, payload):
+        zt_q, st = payload
+        return _ops.QuantCache(self.zi_q, zt_q, self.si, st.reshape(()))
+
+    def unpack(self, payload):
+        zt_q, st = payload
+        chunk = (zt_q.to(torch.float32) * st).to(self.dtype)
+        return chunk, self.qcache(payload)
+
+
+class _RingChunks:
+    """One rank's share of the ring loss: its image block against the text
+    chunks of all ``world`` ranks, added one by one as they arrive.  Plain
+    Python — no autograd, no process group.
+
+    ``regime`` (fixed at construction) says what forward keeps for backward:
+
+    - ``"slab"`` — bf16/mixed saved-g: every chunk's fwd+g kernel writes its
+      dL/dlogit block into ONE ``(b, W·b)`` slab (column offset = source
+      rank; mixed also the ``gᵀ`` slab) and accumulates into one scalar
+      buffer, so backward is pure GEMMs over the concatenated text.
+    - ``"chunk_slabs"`` — fp8 saved-g: the text scales differ per chunk, so
+      each chunk keeps its own g slab and scalars; ``gᵀ`` is still one slab
+      (the image side has one scale).
+    - ``"chunk_recompute"`` — fp8 on GPU without saved g: backward recomputes
+      chunk by chunk.  Both fp8 regimes reuse the forward's per-source
+      quantization — fwd and bwd must see the same quantized values.
+    - ``"concat_recompute"`` — everything else (incl. CPU): one recompute
+      backward over the concatenated text block.
+    """
+
+    _META = ("world", "rank", "b_txt", "quant", "col_chunk", "impl", "regime")
+    # Tensor state by field name: single tensors, and lists indexed by source
+    # rank.  Unused fields stay None and are not saved.
+    _ONE = ("zimg", "t_prime", "bias", "g", "gt", "out3", "zi_q", "si")
+    _PER_SRC = ("chunks", "g_chunks", "out3s", "zt_qs", "sts")
+
+    def __init__(self, zimg, t_prime, bias, world, rank, b_txt, quant,
+                 col_chunk, impl, want_grad):
+        self._restore({}, world=world, rank=rank, b_txt=b_txt, quant=quant,
+                      col_chunk=col_chunk, impl=impl, regime=None)
+        self.zimg, self.t_prime, self.bias = zimg, t_prime, bias
+        b_img, n = zimg.shape[0], world * b_txt
+        on_gpu = zimg.is_cuda and impl != "torch"
+        # want_grad comes from the caller (grad mode is off inside
+        # Function.forward).
+        save_g = (on_gpu and col_chunk is None and want_grad
+                  and _ops.extension_available()
+                  and _ops.save_g_enabled(b_img, n, quant))
+        if save_g:
+            self.regime = "chunk_slabs" if quant == "fp8" else "slab"
+            g_dtype = (torch.bfloat16 if quant == "bf16"
+                       else torch.float8_e4m3fn)
+            if quant != "fp8":
+                self.g = torch.empty((b_img, n), device=zimg.device,
+                                     dtype=g_dtype)
+                self.out3 = _ops._out_buf(zimg.device)
+            if quant != "bf16":
+                self.gt = torch.empty((n, b_img), device=zimg.device,
+                                      dtype=g_dtype)
+        elif quant == "fp8" and on_gpu:
+            self.regime = "chunk_recompute"
+        else:
+            self.regime = "concat_recompute"
+
+    def _restore(self, named, **meta):
+        self.__dict__.update(meta)
+        for k in self._ONE:
+            setattr(self, k, named.get(k))
+        for k in self._PER_SRC:
+            setattr(self, k, [named.get(f"{k}.{s}")
+                              for s in range(self.world)])
+        self._loss = None
+
+    def tensors(self) -> dict:
+        """The populated tensor fields by name, per-source ones as
+        ``field.src`` (``save_for_backward`` the values, keep the keys)."""
+        named = {k: getattr(self, k) for k in self._ONE}
+        for k in self._PER_SRC:
+            named.update({f"{k}.{s}": t
+                          for s, t in enumerate(getattr(self, k))})
+        return {k: t for k, t in named.items() if t is not None}
+
+    def meta(self) -> dict:
+        return {k: getattr(self, k) for k in self._META}
+
+    @classmethod
+    def from_tensors(cls, named, **meta) -> "_RingChunks":
+        """Inverse of :meth:`tensors` + :meth:`meta`, for backward."""
+        self = cls.__new__(cls)
+        self._restore(named, **meta)
+        return self
+
+    def _qc(self, src):
+        return _ops.QuantCache(self.zi_q, self.zt_qs[src], self.si,
+                               self.sts[src])
+
+    def add(self, src, chunk, qc, diag):
+        """Run the loss kernel of source rank ``src``'s text ``chunk`` (``qc``:
+        its fp8 QuantCache or None; ``diag``: 0 for the own block, None for a
+        negatives-only remote one)."""
+        self.chunks[src] = chunk
+        if self.regime in ("chunk_slabs", "chunk_recompute"):
+            # the image side is shared: kept once, not per source
+            self.zi_q, self.si = qc.zi_q, qc.si
+            self.zt_qs[src], self.sts[src] = qc.zt_q, qc.st
+        args = (self.zimg, chunk, self.t_prime, self.bias, diag)
+        col0 = src * self.b_txt
+        if self.regime == "slab":
+            _ops.siglip_fwd_g(*args, quant=self.quant, g_slab=self.g,
+                              gt_slab=self.gt, col0=col0, out3=self.out3)
+        elif self.regime == "chunk_slabs":
+            self.out3s[src], self.g_chunks[src], _ = _ops.siglip_fwd_g(
+                *args, quant=self.quant, qcache=qc, gt_slab=self.gt,
+                col0=col0)
+        else:
+            part = chunk_loss_fwd(*args, col_chunk=self.col_chunk,
+                                  impl=self.impl, quant=self.quant, qcache=qc)
+            self._loss = part if self._loss is None else self._loss + part
+
+    def loss(self):
+        """Finish the forward (call once, after the last ``add``): reduce the
+        per-XCD scalar buffers every chunk's kernel accumulated into."""
+        if self.regime == "slab":
+            self.out3 = _ops.reduce_out3(self.out3)
+            return self.out3[0].clone()
+        if self.regime == "chunk_slabs":
+            self.out3s = [_ops.reduce_out3(o) for o in self.out3s]
+            return sum(o[0] for o in self.out3s).clone()
+        return self._loss
+
+    def grads(self, grad_output, on_dztxt):
+        """``(dzimg, dtxt_flat, dt_prime, dbias)`` with ``dtxt_flat`` the
+        ``(W·b, d)`` gradient of ALL ranks' text, rows in source-rank order;
+        ``on_dztxt(dtxt_flat)`` fires as soon as it exists, before the
+        image-gradient GEMM."""
+        zimg, t_prime, bias = self.zimg, self.t_prime, self.bias
+        world, b, quant = self.world, self.b_txt, self.quant
+        if self.regime == "chunk_slabs":
+            return _ops.siglip_bwd_from_g_chunks(
+                zimg, self.chunks, t_prime, bias, grad_output, self.out3s,
+                self.g_chunks, self.gt, [self._qc(s) for s in range(world)],
+                on_dztxt=on_dztxt)
+        if self.regime == "chunk_recompute":
+            dzimg_acc = torch.zeros_like(zimg, dtype=torch.float32)
+            dtxt_flat = torch.empty((world * b, zimg.shape[1]),
+                                    device=zimg.device, dtype=zimg.dtype)
+            dt_prime = dbias = 0
+            for src in range(world):
+                dzi, dzt, dtp, dbs = chunk_loss_bwd(
+                    zimg, self.chunks[src], t_prime, bias,
+                    0 if src == self.rank else None, grad_output,
+                    col_chunk=self.col_chunk, impl=self.impl, quant=quant,
+                    qcache=self._qc(src))
+                dzimg_acc += dzi.float()
+                dtxt_flat[src * b:(src + 1) * b] = dzt
+                dt_prime, dbias = dt_prime + dtp, dbias + dbs
+            on_dztxt(dtxt_flat)
+            return dzimg_acc.to(zimg.dtype), dtxt_flat, dt_prime, dbias
+        # One (W·b, d) text block: identical math to per-chunk calls, with
+        # the diagonal at the own-rank block.
+        all_txt = (self.chunks[0] if world == 1
+                   else torch.cat(self.chunks, dim=0))
+        if self.regime == "slab":
+            # mixed: g came from exact bf16 logits; quantization only
+            # compresses the grad GEMM operands — one pass here.
+            qc = (_ops.quantize_fp8_pair(zimg, all_txt)
+                  if quant == "mixed" else None)
+            return _ops.siglip_bwd_from_g(
+                zimg, all_txt, t_prime, bias, grad_output, self.out3, self.g,
+                self.gt, quant=quant, qcache=qc, on_dztxt=on_dztxt)
+        return chunk_loss_bwd(
+            zimg, all_txt, t_prime, bias, self.rank * b, grad_output,
+            col_chunk=self.col_chunk, impl=self.impl, quant=quant,
+            on_dztxt=on_dztxt)
+
+
 class _RingAllGatherLoss(torch.autograd.Function):
     """Fused distributed loss: ring-pipelined forward, reduce-scatter backward.
 
-    Forward walks the text shards around a P2P ring — unidirectional, or
-    bidirectional with two xGMI links per hop and ⌈(W−1)/2⌉ hops; the
+    Forward walks the text shards around a P2P ring (``parallel.ring``); the
     exchange of the next chunk is posted *before* the loss kernel for the
     current one runs, so on RCCL the wire time hides under the MFMA compute
-    (the reference serializes these — ``distributed_utils.py:25-26``).  All
-    received shards are kept (O(W·b·d), trivial against 288 GB HBM3E) so
-    backward never re-communicates embeddings.  Each chunk's fwd+g kernel
-    writes its dL/dlogit block into one (b, W·b) slab (saved-g, the default)
-    so backward is pure GEMMs; the recompute path remains for huge batches.
+    (the reference serializes these — ``distributed_utils.py:25-26``).  What
+    travels is the wire format's payload (:class:`_PlainWire` /
+    :class:`_Fp8Wire`); the per-chunk compute and everything kept for
+    backward — all received shards included, so backward never
+    re-communicates embeddings — belong to :class:`_RingChunks`.
 
     Backward produces the full text-gradient block and issues ONE
     ``reduce_scatter_tensor(SUM)`` — the algebraic collapse of the
@@ -94,350 +287,60 @@ class _RingAllGatherLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, zimg, ztxt, t_prime, bias, group, col_chunk, impl,
                 quant, want_grad, bidir=False):
-        from .. import ops as _ops
         world, rank = _world_and_rank(group)
         zimg = zimg.contiguous()
         ztxt = ztxt.contiguous()
-        b_img = zimg.shape[0]
-        b_txt = ztxt.shape[0]
-
-        chunks = [None] * world          # indexed by source rank
-        chunks[rank] = ztxt
-
-        on_gpu = zimg.is_cuda and impl != "torch"
-        # saved-g: each chunk's fwd+g kernel writes its dL/dlogit block
-        # straight into one (b, W·b) slab (column offset = source rank), so
-        # backward is pure GEMMs — no logits recompute anywhere in the step.
-        # want_grad comes from the caller (grad mode is off inside
-        # Function.forward).
-        save_g = (on_gpu and col_chunk is None and want_grad
-                  and _ops.extension_available()
-                  and _ops.save_g_enabled(b_img, world * b_txt, quant))
-
-        # fp8: quantize BOTH own shards ONCE and ship e4m3 + scale over the
-        # wire — half the xGMI bytes per hop versus bf16, no per-chunk
-        # quantize kernels, and every rank computes with the exact
-        # quantized values the owner produced.  Per-chunk scales are SAVED
-        # for backward so fwd and bwd see identical quantized values (the
-        # round-1 version requantized the concatenated block with one
-        # scale — fwd/bwd loss surfaces differed at W>1).
-        fp8_wire = quant == "fp8" and world > 1
-        use_q = quant == "fp8" and on_gpu
-        qcaches = [None] * world        # per-source ops.QuantCache
-        if quant == "fp8":
-            zi_q, si = _ops._quant_fp8(zimg)
-            zt_q0, st0 = _ops._quant_fp8(ztxt)
-
-            def dequant(q8, sc):
-                return (q8.to(torch.float32) * sc).to(zimg.dtype)
-
-            def qc_of(q8, sc):
-                return _ops.QuantCache(zi_q, q8, si, sc.reshape(()))
-        else:
-            zt_q0 = st0 = None
-
-        def qc_for(zt_chunk):
-            # own-rank / non-wire chunks only (wire chunks carry their
-            # quantization with them)
-            if quant != "fp8":
-                return None
-            if zt_chunk is ztxt:
-                return qc_of(zt_q0, st0)
-            return qc_of(*_ops._quant_fp8(zt_chunk))
-
-        g_slab = gt_slab = out3 = None
-        g_chunks = [None] * world       # fp8: per-chunk g (scales differ)
-        out3s = [None] * world
-        if save_g:
-            esz = 1 if quant in ("fp8", "mixed") else 2
-            g_dtype = (torch.float8_e4m3fn if esz == 1 else torch.bfloat16)
-            if quant != "fp8":
-                g_slab = torch.empty((b_img, world * b_txt),
-                                     device=zimg.device, dtype=g_dtype)
-                out3 = _ops._out_buf(zimg.device)
-            if quant in ("fp8", "mixed"):
-                gt_slab = torch.empty((world * b_txt, b_img),
-                                      device=zimg.device, dtype=g_dtype)
-
-        def chunk_fwd(zt_chunk, src, diag, qc=None):
-            if qc is None:
-                qc = qc_for(zt_chunk)
-            qcaches[src] = qc
-            if not save_g:
-                return chunk_loss_fwd(zimg, zt_chunk, t_prime, bias,
-                                      diag_offset=diag, col_chunk=col_chunk,
-                                      impl=impl, quant=quant, qcache=qc)
-            if quant == "fp8":
-                o3, g_c, _ = _ops.siglip_fwd_g(
-                    zimg, zt_chunk, t_prime, bias, diag, quant=quant,
-                    qcache=qc, gt_slab=gt_slab, col0=src * b_txt)
-                g_chunks[src] = g_c
-                out3s[src] = o3
-                return None
-            _ops.siglip_fwd_g(
-                zimg, zt_chunk, t_prime, bias, diag, quant=quant,
-                g_slab=g_slab, gt_slab=gt_slab, col0=src * b_txt, out3=out3)
-            return None   # shared out3 accumulates across chunks
-
-        # Wire payload abstraction: bf16/mixed ship the chunk tensor; fp8
-        # ships its (e4m3-as-uint8, fp32 scale) pair.  unpack() returns the
-        # compute-dtype chunk plus the per-chunk qcache.
-        if fp8_wire:
-            def wire_uni(payload):
-                return quantized_exchange_start(left, right, payload[0],
-                                                payload[1], group=group)
-
-            def wire_bidir(pl, pr):
-                return quantized_exchange_bidir_start(
-                    left, right, pl[0], pl[1], pr[0], pr[1], group=group)
-
-            def unpack(recvs):
-                q8 = recvs[0].view(torch.float8_e4m3fn)
-                sc = recvs[1]
-                return dequant(q8, sc), qc_of(q8, sc), (q8, sc)
-
-            own_payload = (zt_q0, st0.reshape(1).float())
-        else:
-            def wire_uni(payload):
-                return neighbour_exchange_start(left, right, payload,
-                                                group=group)
-
-            def wire_bidir(pl, pr):
-                return neighbour_exchange_bidir_start(left, right, pl, pr,
-                                                      group=group)
-
-            def unpack(recvs):
-                return recvs[0], None, recvs[0]
-
-            own_payload = ztxt
-
-        use_bidir = bidir and world > 2
-        if world > 1:
-            left = (rank - 1 + world) % world
-            right = (rank + 1) % world
-            if group is not None:
-                # P2POp peers are GLOBAL ranks even when a group is given;
-                # rank/left/right above are group-local.  Identity for the
-                # default group, required for subgroups like {1, 2}.
-                left = dist.get_global_rank(group, left)
-                right = dist.get_global_rank(group, right)
-            # Post hop 1 before any compute: its wire time hides under the
-            # local-block kernel below.  The bidirectional variant drives
-            # TWO xGMI point-to-point links per hop (reference
-            # distributed_utils.py:30-62 at the perf layer), halving the hop
-            # count to ⌈(W−1)/2⌉ — at N=8 per-rank b=4096 the ring is
-            # wire-bound, so hop count and bytes per hop are the levers.
-            if use_bidir:
-                handle = wire_bidir(own_payload, own_payload)
-            else:
-                handle = wire_uni(own_payload)
-
-        loss = chunk_fwd(ztxt, rank, 0)
-
-        def add_part(part):
-            nonlocal loss
-            if part is not None:
-                loss = loss + part
-
-        def take(recvs, src):
-            chunk, qc, payload = unpack(recvs)
-            chunks[src] = chunk
-            return chunk, qc, payload
-
-        if world > 1 and use_bidir:
-            nb, rem = divmod(world - 1, 2)
-            npl = 2 if fp8_wire else 1    # tensors per direction on the wire
-            for r in range(1, nb + 1):
-                with _hop_span(f"ring_bhop{r}_wait"):
-                    recvs = handle.wait()
-                src_r = (rank + r) % world
-                src_l = (rank - r + world) % world
-                from_right, qc_r, pl_r = take(recvs[:npl], src_r)
-                from_left, qc_l, pl_l = take(recvs[npl:], src_l)
-                if r < nb:
-                    handle = wire_bidir(pl_r, pl_l)
-                elif rem:
-                    # one unidirectional remainder hop: forward the
-                    # rightward-traveling stream (last received from left)
-                    handle = wire_uni(pl_l)
-                with _hop_span(f"ring_bchunk{r}_loss"):
-                    add_part(chunk_fwd(from_right, src_r, None, qc_r))
-                    add_part(chunk_fwd(from_left, src_l, None, qc_l))
-            if rem:
-                with _hop_span("ring_rem_wait"):
-                    recvs = handle.wait()
-                src = (rank - nb - 1 + world) % world
-                recv, qc, _ = take(recvs, src)
-                add_part(chunk_fwd(recv, src, None, qc))
-        elif world > 1:
-            for hop in range(1, world):
-                # Post hop k+1 before computing on hop k's data.  roctx
-                # ranges label the hops for rocprofv3/torch.profiler traces
-                # (per-hop comm visibility).
-                with _hop_span(f"ring_hop{hop}_wait"):
-                    recvs = handle.wait()
-                src = (rank - hop + world) % world
-                recv, qc, payload = take(recvs, src)
-                if hop < world - 1:
-                    handle = wire_uni(payload)
-                with _hop_span(f"ring_chunk{hop}_loss"):
-                    add_part(chunk_fwd(recv, src, None, qc))
-
-        if save_g:
-            # Reduce the per-XCD scalar buffers once, after every chunk's
-            # kernel has accumulated into them.
-            if quant == "fp8":
-                out3s = [_ops.reduce_out3(o) for o in out3s]
-                loss = sum(o[0] for o in out3s).clone()
-            else:
-                out3 = _ops.reduce_out3(out3)
-                loss = out3[0].clone()
-
-        saved = [zimg, t_prime, bias] + chunks
-        idx = {}
-        extra = []
-        if save_g:
-            if quant == "fp8":
-                idx["g_chunks"] = len(extra)
-                extra += g_chunks
-                idx["out3s"] = len(extra)
-                extra += out3s
-                idx["gt_slab"] = len(extra)
-                extra.append(gt_slab)
-            else:
-                idx["g_slab"] = len(extra)
-                extra.append(g_slab)
-                idx["out3"] = len(extra)
-                extra.append(out3)
-                if gt_slab is not None:
-                    idx["gt_slab"] = len(extra)
-                    extra.append(gt_slab)
-        if use_q:
-            # one per-tensor cache per source (the image side is shared;
-            # saving the same tensor again costs nothing)
-            idx["qcaches"] = len(extra)
-            for qc in qcaches:
-                extra += qc.tensors()
-        ctx.save_for_backward(*saved, *extra)
-        ctx.extra_idx = idx
-        ctx.save_g = save_g
+        wire = _Fp8Wire(zimg) if quant == "fp8" else _PlainWire()
+        own = wire.pack(ztxt)
+        acc = _RingChunks(zimg, t_prime, bias, world, rank, ztxt.shape[0],
+                          quant, col_chunk, impl, want_grad)
+        ring = walk_ring(own, world, rank, bidir, group)
+        next(ring)      # hop 1 is on the wire before the local-block kernel
+        acc.add(rank, ztxt, wire.qcache(own), 0)
+        for label, arrived in ring:
+            # hop k+1 is already posted; these kernels hide its wire time
+            got = [(src,) + wire.unpack(payload) for src, payload in arrived]
+            with hop_span(label):
+                for src, chunk, qc in got:
+                    acc.add(src, chunk, qc, None)
+        loss = acc.loss()
+        named = acc.tensors()
+        ctx.save_for_backward(*named.values())
+        ctx.names = tuple(named)
+        ctx.meta = acc.meta()
         ctx.group = group
-        ctx.world = world
-        ctx.rank = rank
-        ctx.col_chunk = col_chunk
-        ctx.impl = impl
-        ctx.quant = quant
-        ctx.b_txt = b_txt
         return loss
 
     @staticmethod
     def backward(ctx, grad_output):
-        from .. import ops as _ops
-        world, rank = ctx.world, ctx.rank
-        b = ctx.b_txt
-        zimg, t_prime, bias = ctx.saved_tensors[:3]
-        chunks = ctx.saved_tensors[3:3 + world]
-        extra = ctx.saved_tensors[3 + world:]
-        idx = ctx.extra_idx
-        quant = ctx.quant
+        acc = _RingChunks.from_tensors(
+            dict(zip(ctx.names, ctx.saved_tensors)), **ctx.meta)
+        world, rank, b = acc.world, acc.rank, acc.b_txt
 
-        # The cross-rank reduce-scatter (the collapse of the reference's
-        # W−1 reversed ring hops, distributed_utils.py:74-77, into one RCCL
-        # collective) is launched ASYNC from the on_dztxt hook, so its xGMI
-        # wire time overlaps the dzimg gradient GEMM(s) still running on
-        # the compute stream.
-        comm = {}
+        # The cross-rank reduce-scatter is launched ASYNC from the on_dztxt
+        # hook, so its xGMI wire time overlaps the dzimg gradient GEMM(s)
+        # still running on the compute stream.
+        gloo = world > 1 and _backend_is_gloo(ctx.group)
+        pending = []
 
         def on_dztxt(flat):
             if world == 1:
                 return
-            if _backend_is_gloo(ctx.group):
-                comm["work"] = dist.all_reduce(
-                    flat, op=dist.ReduceOp.SUM, group=ctx.group,
-                    async_op=True)
-                comm["flat"] = flat
+            if gloo:    # no reduce-scatter: all-reduce, keep the own slice
+                out = flat[rank * b:(rank + 1) * b]
+                work = dist.all_reduce(flat, op=dist.ReduceOp.SUM,
+                                       group=ctx.group, async_op=True)
             else:
                 out = torch.empty_like(flat[:b])
-                comm["work"] = dist.reduce_scatter_tensor(
+                work = dist.reduce_scatter_tensor(
                     out, flat, op=dist.ReduceOp.SUM, group=ctx.group,
                     async_op=True)
-                comm["out"] = out
+            pending.append((work, out))
 
-        go = grad_output
-        if ctx.save_g and quant != "fp8":
-            # One slab: dztxt_flat = t·go·(gᵀ @ zimg) first (feeds the async
-            # reduce-scatter), then dzimg = t·go·(g @ concat-text).
-            all_txt = chunks[0] if world == 1 else torch.cat(chunks, dim=0)
-            out3 = extra[idx["out3"]]
-            g = extra[idx["g_slab"]]
-            gt = extra[idx["gt_slab"]] if "gt_slab" in idx else None
-            qc = None
-            if quant == "mixed":
-                # mixed: g came from exact bf16 logits; quantization only
-                # compresses the grad GEMM operands — one pass here.
-                qc = _ops.quantize_fp8_pair(zimg, all_txt)
-            dzimg, dtxt_flat, dt_prime, dbias = _ops.siglip_bwd_from_g(
-                zimg, all_txt, t_prime, bias, go, out3, g, gt,
-                quant=quant, qcache=qc, on_dztxt=on_dztxt)
-        elif quant == "fp8" and "qcaches" in idx:
-            # fp8 keeps per-chunk text scales (never requantize — fwd/bwd
-            # must see the same quantized values), so both regimes walk the
-            # chunks with the forward's own per-source caches.
-            qts = extra[idx["qcaches"]:]
-            qcs = [_ops.QuantCache.from_tensors(qts[4 * s:4 * s + 4])
-                   for s in range(world)]
-            dt_prime = dbias = 0
-            if ctx.save_g:
-                # saved-g: the image side has one scale, so dztxt is still a
-                # single GEMM over the full gt slab.
-                g_chunks = extra[idx["g_chunks"]:idx["g_chunks"] + world]
-                out3s = extra[idx["out3s"]:idx["out3s"] + world]
-                go32 = go.detach().reshape(()).to(zimg.device).float()
-                t_true = t_prime.detach().reshape(()).float().exp()
-                dzimg, dtxt_flat = _ops.grad_gemms(
-                    [_ops.GBand(g_c, None, zt, qc)
-                     for g_c, zt, qc in zip(g_chunks, chunks, qcs)],
-                    zimg, world * b, go32 * t_true, on_dztxt=on_dztxt,
-                    gt_full=extra[idx["gt_slab"]])
-                for o3, qc in zip(out3s, qcs):
-                    dtp, dbs = _ops.scalar_grads(
-                        o3, go32, t_true * qc.si * qc.st, t_prime, bias)
-                    dt_prime, dbias = dt_prime + dtp, dbias + dbs
-            else:
-                dzimg_acc = torch.zeros_like(zimg, dtype=torch.float32)
-                dtxt_flat = torch.empty((world * b, zimg.shape[1]),
-                                        device=zimg.device, dtype=zimg.dtype)
-                for src in range(world):
-                    dzi, dzt, dtp, dbs = chunk_loss_bwd(
-                        zimg, chunks[src], t_prime, bias,
-                        0 if src == rank else None, go,
-                        col_chunk=ctx.col_chunk, impl=ctx.impl, quant=quant,
-                        qcache=qcs[src])
-                    dzimg_acc += dzi.float()
-                    dtxt_flat[src * b:(src + 1) * b] = dzt
-                    dt_prime, dbias = dt_prime + dtp, dbias + dbs
-                on_dztxt(dtxt_flat)
-                dzimg = dzimg_acc.to(zimg.dtype)
-        else:
-            # bf16/mixed recompute: one fused backward over the concatenated
-            # (W·b, d) text block — identical math to per-chunk calls (diag
-            # at the own-rank block), a single dzimg accumulator and one
-            # slab loop.
-            all_txt = chunks[0] if world == 1 else torch.cat(chunks, dim=0)
-            dzimg, dtxt_flat, dt_prime, dbias = chunk_loss_bwd(
-                zimg, all_txt, t_prime, bias, rank * b, go,
-                col_chunk=ctx.col_chunk, impl=ctx.impl, quant=quant,
-                on_dztxt=on_dztxt)
-
-        if world > 1:
-            comm["work"].wait()
-            if "out" in comm:
-                dztxt = comm["out"]
-            else:
-                dztxt = comm["flat"][rank * b:(rank + 1) * b].clone()
-        else:
-            dztxt = dtxt_flat
-
+        dzimg, dztxt, dt_prime, dbias = acc.grads(grad_output, on_dztxt)
+        for work, out in pending:
+            work.wait()
+            dztxt = out.clone() if gloo else out
         return (dzimg, dztxt, dt_prime, dbias, None, None, None, None, None,
                 None)
 

@@ -941,6 +941,30 @@ def siglip_bwd_from_g(zimg: torch.Tensor, ztxt: torch.Tensor,
     return (dzimg, dztxt) + scalar_grads(out3, go, t_eff, t_prime, bias)
 
 
+def siglip_bwd_from_g_chunks(zimg: torch.Tensor, chunks, t_prime: torch.Tensor,
+                             bias: torch.Tensor, grad_output: torch.Tensor,
+                             out3s, g_chunks, gt: torch.Tensor, qcaches,
+                             on_dztxt=None):
+    """Backward from per-chunk saved g (the fp8 ring): text ``chunks`` in row
+    order, each with its own e4m3 slab, REDUCED ``out3`` and per-tensor
+    :class:`QuantCache` (text scales differ per chunk, the image side is
+    shared), plus the one ``(n, b)`` transpose slab ``gt`` — dztxt is a single
+    GEMM.  Same return contract as :func:`siglip_bwd_from_g`."""
+    t_true = _prep_scalar(t_prime, zimg.device).exp()
+    go = grad_output.detach().reshape(()).to(device=zimg.device,
+                                             dtype=torch.float32)
+    dzimg, dztxt = grad_gemms(
+        [GBand(g, None, zt, qc)
+         for g, zt, qc in zip(g_chunks, chunks, qcaches)],
+        zimg, gt.shape[0], go * t_true, on_dztxt=on_dztxt, gt_full=gt)
+    dt_prime = dbias = 0
+    for out3, qc in zip(out3s, qcaches):
+        dtp, dbs = scalar_grads(out3, go, t_true * qc.si * qc.st, t_prime,
+                                bias)
+        dt_prime, dbias = dt_prime + dtp, dbias + dbs
+    return dzimg, dztxt, dt_prime, dbias
+
+
 def siglip_bwd_banded(zimg: torch.Tensor, ztxt: torch.Tensor,
                       t_prime: torch.Tensor, bias: torch.Tensor,
                       grad_output: torch.Tensor, out3: torch.Tensor,

@@ -5,8 +5,9 @@ from .ring import (
     neighbour_exchange_bidir_with_grad,
     neighbour_exchange_start,
     neighbour_exchange_bidir_start,
-    quantized_exchange_start,
-    quantized_exchange_bidir_start,
+    exchange_start,
+    ring_schedule,
+    walk_ring,
     NeighbourExchange,
     NeighbourExchangeBidir,
     RingHandle,
@@ -20,8 +21,9 @@ __all__ = [
     "neighbour_exchange_bidir_with_grad",
     "neighbour_exchange_start",
     "neighbour_exchange_bidir_start",
-    "quantized_exchange_start",
-    "quantized_exchange_bidir_start",
+    "exchange_start",
+    "ring_schedule",
+    "walk_ring",
     "NeighbourExchange",
     "NeighbourExchangeBidir",
     "RingHandle",

@@ -2,6 +2,7 @@
 + scalar partials, backward is pure GEMMs.  Verifies it against both the
 recompute kernels and the fp32 PyTorch reference."""
 
+import functools
 import math
 import os
 
@@ -378,6 +379,175 @@ def test_fp8_ring_recompute_single_gpu(b):
     for a, b_ in zip(results["ring"], results["plain"]):
         assert torch.allclose(a.float(), b_.float(), rtol=5e-2, atol=5e-3), \
             (a.float() - b_.float()).abs().max()
+
+
+# ---------------------------------------------------------------------------
+# The ring's chunk accumulator (_RingChunks) and wire formats driven directly
+# on one GPU, no process group: W=3, rank=1 (the positive diagonal sits in the
+# middle block), chunks added in bidirectional arrival order (own, right,
+# left).  The oracle is the plain fused loss over the concatenated text on the
+# same device in the same regime.
+#
+# Inputs follow tests/test_gpu_tile_exact.py's informative regime,
+# t' = log(1.5 / std(dot)) and bias = -0.5, so the negatives carry weight: a
+# dropped or misplaced chunk moves every output by tens of percent.  For fp8
+# the three text chunks are scaled by distinct factors in [2/3, 3/2]: their
+# per-tensor scales differ by 1.5x steps, and a mispaired scale is visible.
+# ---------------------------------------------------------------------------
+
+RING_W, RING_RANK, RING_D = 3, 1, 128
+RING_ORDER = (1, 2, 0)
+RING_FACTORS = {"fp8": (2.0 / 3.0, 1.0, 1.5)}
+RING_NAMES = ("loss", "dzimg", "dtxt_flat", "dt_prime", "dbias")
+
+
+@functools.lru_cache(maxsize=None)
+def _ring_case(b, scaled):
+    """Inputs plus the float64 reference (loss, grads, informative fraction),
+    computed once per key from the bf16 values and never modified."""
+    gen = torch.Generator().manual_seed(7000 + b)
+    factors = RING_FACTORS["fp8"] if scaled else (1.0,) * RING_W
+    zi = F.normalize(torch.randn(b, RING_D, generator=gen), dim=-1)
+    chunks = [F.normalize(torch.randn(b, RING_D, generator=gen), dim=-1) * f
+              for f in factors]
+    zi = zi.cuda().bfloat16()
+    chunks = tuple(c.cuda().bfloat16() for c in chunks)
+    zi64 = zi.double().requires_grad_(True)
+    zt64 = torch.cat(chunks).double().requires_grad_(True)
+    dot = (zi64 @ zt64.T).detach()
+    tp64 = torch.tensor(math.log(1.5 / float(dot.std())), device="cuda",
+                        dtype=torch.float64, requires_grad=True)
+    bs64 = torch.tensor(-0.5, device="cuda", dtype=torch.float64,
+                        requires_grad=True)
+    diag = RING_RANK * b
+    loss = _torch_loss(zi64, zt64, tp64, bs64, diag, col_chunk=None)
+    loss.backward()
+    lab = -torch.ones_like(dot)
+    i = torch.arange(b, device="cuda")
+    lab[i, i + diag] = 1.0
+    g = torch.sigmoid(-lab * (dot * tp64.detach().exp() + bs64.detach()))
+    informative = float(((g >= 0.05) & (g <= 0.95)).double().mean())
+    ref = (loss.detach(), zi64.grad, zt64.grad, tp64.grad, bs64.grad)
+    return (zi, chunks, tp64.detach().float(), bs64.detach().float(), ref,
+            informative)
+
+
+def _ring_run(b, quant, want_grad=True):
+    """Drive wire + accumulator as _RingAllGatherLoss does → (acc, outputs)."""
+    from distributed_sigmoid_loss_amd.losses.sigmoid_loss import (
+        _Fp8Wire, _PlainWire, _RingChunks)
+    zi, chunks, tp, bs, _, _ = _ring_case(b, quant == "fp8")
+    wire = _Fp8Wire(zi) if quant == "fp8" else _PlainWire()
+    payloads = [wire.pack(c) for c in chunks]     # each owner's quantization
+    acc = _RingChunks(zi, tp, bs, RING_W, RING_RANK, b, quant, None, "auto",
+                      want_grad)
+    for src in RING_ORDER:
+        if src == RING_RANK:
+            acc.add(src, chunks[src], wire.qcache(payloads[src]), 0)
+        else:
+            acc.add(src, *wire.unpack(payloads[src]), None)
+    loss = acc.loss()
+    if not want_grad:
+        torch.cuda.synchronize()
+        return acc, (loss,)
+    # backward sees only what a Function would have saved
+    back = _RingChunks.from_tensors(acc.tensors(), **acc.meta())
+    fired = []
+    grads = back.grads(torch.ones((), device="cuda"), fired.append)
+    torch.cuda.synchronize()
+    assert len(fired) == 1 and fired[0] is grads[1]
+    return acc, (loss,) + tuple(grads)
+
+
+def _plain_run(b, quant):
+    zi, chunks, tp, bs, _, _ = _ring_case(b, quant == "fp8")
+    zi, zt, tp, bs = (t.clone().requires_grad_(True)
+                      for t in (zi, torch.cat(chunks), tp, bs))
+    loss = sigmoid_contrastive_loss(zi, zt, tp, bs,
+                                    diag_offset=RING_RANK * b, quant=quant)
+    loss.backward()
+    torch.cuda.synchronize()
+    return loss.detach(), zi.grad, zt.grad, tp.grad, bs.grad
+
+
+def _err(a, b_, ref):
+    """‖a − b‖ / ‖ref‖ in float64 (|·| for scalars)."""
+    return float((a.double() - b_.double()).norm() / ref.double().norm())
+
+
+def _set_regime(monkeypatch, save_g):
+    monkeypatch.delenv("SIGLIP_FP8_ROWWISE", raising=False)
+    if save_g:
+        monkeypatch.delenv("SIGLIP_SAVE_G", raising=False)
+    else:
+        monkeypatch.setenv("SIGLIP_SAVE_G", "0")
+
+
+@pytest.mark.parametrize("save_g", [True, False], ids=["savedg", "recompute"])
+@pytest.mark.parametrize("quant", ["bf16", "mixed"])
+@pytest.mark.parametrize("b", [256, 260])   # interior tiles / ragged edge
+def test_ring_chunks_match_plain(b, quant, save_g, monkeypatch):
+    """bf16/mixed: the accumulator launches the plain path's kernels on the
+    same bits (test_fwdg_slab_offset_write: the chunked slab is torch.equal to
+    the single-call one) and makes the same GEMM calls.  Scalars come out of
+    atomics, so they get that test's tolerance; the gradient tensors must
+    agree to one bf16 unit roundoff normwise (2^-8) — exact equality is
+    expected, anything larger is a bug."""
+    _set_regime(monkeypatch, save_g)
+    *_, ref, informative = _ring_case(b, False)
+    assert informative >= 0.9, informative
+    acc, ring = _ring_run(b, quant)
+    assert acc.regime == ("slab" if save_g else "concat_recompute")
+    plain = _plain_run(b, quant)
+    for name, r, p in zip(RING_NAMES, ring, plain):
+        print(f"{name}: ring-vs-plain {_err(r, p, p):.3e}")
+    for name, r, p in zip(RING_NAMES, ring, plain):
+        if name in ("dzimg", "dtxt_flat"):
+            assert _err(r, p, p) <= 2.0 ** -8, name
+        else:
+            assert torch.allclose(r.float(), p.float(), rtol=1e-3,
+                                  atol=1e-3), name
+
+
+@pytest.mark.parametrize("save_g", [True, False], ids=["savedg", "recompute"])
+@pytest.mark.parametrize("b", [256, 260])   # 260: the dequantize-GEMM route
+def test_ring_chunks_fp8_match_plain(b, save_g, monkeypatch):
+    """fp8: the ring quantizes each text chunk with its owner's scale, the
+    plain path the whole block with one, so the two are independently rounded
+    results.  Per output, q = ‖plain − ref64‖/‖ref64‖ is the quantization
+    floor of code the ring does not touch; two results each within about q of
+    exact are within 2q of each other (triangle inequality), so the bound is
+    ‖ring − plain‖/‖ref64‖ <= 2q.  A dropped chunk (~50 %) or a scale
+    mispaired by >= 1.5x is far above it."""
+    _set_regime(monkeypatch, save_g)
+    *_, ref, informative = _ring_case(b, True)
+    assert informative >= 0.9, informative
+    acc, ring = _ring_run(b, "fp8")
+    assert acc.regime == ("chunk_slabs" if save_g else "chunk_recompute")
+    plain = _plain_run(b, "fp8")
+    figures = [(name, _err(p, f, f), _err(r, p, f))
+               for name, r, p, f in zip(RING_NAMES, ring, plain, ref)]
+    for name, q, e in figures:
+        print(f"{name}: q {q:.3e}  ring-vs-plain {e:.3e}")
+    for name, q, e in figures:
+        assert e <= 2 * q, (name, q, e)
+
+
+def test_ring_chunks_no_grad_takes_scalar_forward(monkeypatch):
+    """want_grad=False: no slab is allocated or kept, every chunk runs the
+    scalar-only forward kernel, and the loss equals the saved-g loss."""
+    _set_regime(monkeypatch, True)
+    b = 260
+    *_, informative = _ring_case(b, False)
+    assert informative >= 0.9, informative
+    acc, (loss,) = _ring_run(b, "bf16", want_grad=False)
+    assert acc.regime == "concat_recompute"
+    assert acc.g is None and acc.out3 is None
+    assert set(acc.tensors()) == {"zimg", "t_prime", "bias", "chunks.0",
+                                  "chunks.1", "chunks.2"}
+    acc_g, ring_g = _ring_run(b, "bf16")
+    assert acc_g.regime == "slab"
+    assert torch.allclose(loss, ring_g[0], rtol=1e-3, atol=1e-3)
 
 
 def test_inference_skips_slab():

@@ -108,23 +108,22 @@ def test_exchange_bidir_grad_routing():
 
 
 def _quantized_roundtrip(rank, world):
-    from distributed_sigmoid_loss_amd.parallel.ring import (
-        quantized_exchange_start,
-    )
+    from distributed_sigmoid_loss_amd.parallel.ring import exchange_start
     left = (rank - 1 + world) % world
     right = (rank + 1) % world
     x = torch.randn(8, 16) * (rank + 1)
     from distributed_sigmoid_loss_amd import ops
     q, s = ops._quant_fp8(x)
-    h = quantized_exchange_start(left, right, q, s.reshape(1).float())
-    rq_u8, rs = h.wait()
-    rq = rq_u8.view(torch.float8_e4m3fn)
+    h = exchange_start(left, right, to_right=(q, s.reshape(1).float()))
+    from_right, (rq, rs) = h.wait()
+    assert from_right == () and rq.dtype == torch.float8_e4m3fn
     # verify by echoing: exchange back and compare bitwise with what we sent
-    h2 = quantized_exchange_start(right, left, rq, rs)
-    back_q, back_s = h2.wait()
+    h2 = exchange_start(left, right, to_left=(rq, rs))
+    (back_q, back_s), from_left = h2.wait()
+    assert from_left == ()
     if world == 2:
         # two hops around a 2-ring returns our own payload
-        assert torch.equal(back_q, q.view(torch.uint8))
+        assert torch.equal(back_q.view(torch.uint8), q.view(torch.uint8))
         assert torch.equal(back_s, s.reshape(1).float())
     assert rq.shape == q.shape and float(rs[0]) > 0
     return True

@@ -88,6 +88,13 @@ def _kernel_flags(default_gm: str = "4") -> int:
         f |= 4
     gm = os.environ.get("SIGLIP_GROUP_M", default_gm)
     f |= {"8": 0, "1": 1, "4": 2, "16": 3}.get(gm, 0) << 4
+    # bits 8-23: workgroup cap of the persistent bf16 interior kernel
+    #        (SIGLIP_TILE_WGS; 0 / unset = min(tiles, CUs)) — tests, sweeps.
+    # bit 24: SIGLIP_PERSISTENT=0 launches the same kernel with one tile per
+    #        workgroup, for A/B runs.
+    f |= (int(os.environ.get("SIGLIP_TILE_WGS", "0")) & 0xffff) << 8
+    if os.environ.get("SIGLIP_PERSISTENT", "1") == "0":
+        f |= 1 << 24
     return f
 
 _lib = None
@@ -141,9 +148,9 @@ def _load():
         _lib_err = f"failed to load {SO_PATH}: {e}"
         return None
     lib.siglip_ext_abi.restype = ctypes.c_int
-    if lib.siglip_ext_abi() != 11:
+    if lib.siglip_ext_abi() != 12:
         _lib_err = (f"stale HIP extension at {SO_PATH} "
-                    f"(ABI {lib.siglip_ext_abi()}, need 11); rebuild with: "
+                    f"(ABI {lib.siglip_ext_abi()}, need 12); rebuild with: "
                     "python -m distributed_sigmoid_loss_amd.ops.build --force")
         return None
     # (stream, mode, eb, eb_g, 11 pointers, b, n, d, ldg, diag, flags)

@@ -58,6 +58,20 @@
 //   - Block-id remap (flags): bit0 = XCD-contiguous spans, bit1 = grouped
 //     column-major walk — temporally-close blocks share operand panels in
 //     the per-XCD L2 (measured best together: +4%).
+//   - Epilogue (all modes and dtypes): exp2 and log2 are the bare
+//     v_exp_f32 / v_log_f32 (the log argument 1+y stays in (1,2]; the log2
+//     sum meets ln 2 once per tile); the label predicate is block-uniform —
+//     a tile that cannot hold a positive pair runs a body without it in the
+//     interior kernels, the rest compare one per-lane constant; where the
+//     bf16 g slab stages through LDS the MFMA operands are exchanged so a
+//     lane packs 4 consecutive g columns into one ds_write_b64.
+//   - bf16 interior shapes run a PERSISTENT kernel
+//     (siglip_tile_kernel_persistent): min(tiles, CUs) workgroups walk the
+//     tile list with one K-stream across tile boundaries, per-wave g
+//     staging above the operand buffers (no block barrier in the epilogue)
+//     and one scalar reduction + three atomics per workgroup.  The e4m3-g
+//     instantiations (g + gᵀ staging needs all of LDS) and the edge kernel
+//     stay one tile per workgroup.
 //
 // Host interface: every instantiation of the tile kernel is reached through
 // ONE exported function of fixed signature, siglip_tile(stream, mode, eb,
@@ -72,8 +86,10 @@
 #include <hip/hip_fp8.h>
 #include <cstdint>
 #include <climits>
+#include <type_traits>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
@@ -96,12 +112,18 @@ constexpr int OUT_STRIDE = 32;   // floats per XCD slot of the scalar-output
                                  // buffer (128 B = one cache line)
 constexpr int GROUP_M = 8;       // block-rows per locality group (bit1)
 
-// softplus via the inlined fast log/exp (log1pf is a device-lib CALL —
-// measured as s_getpc/s_setpc pairs inside the epilogue).  For y = e^{-|x|}
-// ∈ (0,1] the naive log(1+y) loses only ~y·ε absolute accuracy near y→0,
-// where the term itself vanishes — fine at bf16-class tolerances.
-__device__ __forceinline__ float softplus_f(float x) {
-  return fmaxf(x, 0.0f) + __logf(1.0f + __expf(-fabsf(x)));
+// softplus(x) = max(x,0) + log(1+y), y = e^{-|x|} ∈ (0,1].  The log argument
+// never leaves (1, 2], so the bare v_log_f32 (log2, ~1 ulp) needs none of
+// __logf's denormal pre-scale / compensated ln2 multiply / range guards
+// (about eleven VALU per element in the ISA; log1pf is a device-lib CALL).
+// The two parts go to separate per-lane sums: the log2 sum is multiplied by
+// ln 2 ONCE per tile when it is folded into the loss partial.  The naive
+// 1+y loses only ~y·ε absolute accuracy near y→0, where the term vanishes.
+constexpr float LN2_F = 0.693147180559945309f;
+__device__ __forceinline__ void softplus_acc(float x, float y, float& s_relu,
+                                             float& s_log2) {
+  s_relu += fmaxf(x, 0.0f);
+  s_log2 += __builtin_amdgcn_logf(1.0f + y);
 }
 
 __device__ __forceinline__ float sigmoid_fast(float negz) {
@@ -157,6 +179,11 @@ __device__ __forceinline__ i32x8 pack8(const uint4 lo, const uint4 hi) {
 }
 
 // One bf16 K-half (32 elements): 32 MFMAs from the swizzled LDS image.
+// SWAP exchanges the MFMA operands: the accumulators then hold the
+// TRANSPOSED 16×16 fragments (row = lane&15 is the image row, the 4 regs are
+// 4 consecutive text columns (lane>>4)*4+reg).  The k order inside each MFMA
+// is unchanged, so every dot is the same sum in the same order.
+template <bool SWAP>
 __device__ __forceinline__ void mma_half_bf16(const char* smem, int aAddr,
                                               int bAddr,
                                               f32x4 (&acc)[FM][FN]) {
@@ -173,8 +200,11 @@ __device__ __forceinline__ void mma_half_bf16(const char* smem, int aAddr,
   for (int mi = 0; mi < FM; ++mi)
 #pragma unroll
     for (int ni = 0; ni < FN; ++ni)
-      acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          afrag[mi], bfrag[ni], acc[mi][ni], 0, 0, 0);
+      acc[mi][ni] = SWAP
+          ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                bfrag[ni], afrag[mi], acc[mi][ni], 0, 0, 0)
+          : __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                afrag[mi], bfrag[ni], acc[mi][ni], 0, 0, 0);
 }
 
 // One fp8 K-step (128 elements): MX-scaled MFMA.  sA/sB are per-fragment
@@ -214,8 +244,10 @@ __device__ __forceinline__ void mma_ktile_fp8(const char* smem,
 
 // g-slab element bytes follow the compute dtype: bf16 kernels emit bf16 g,
 // fp8 kernels emit e4m3 g (×448 fixed scale).
+// SPLIT_POS (interior-only kernel): tiles that cannot hold a positive pair
+// take an epilogue body compiled without the label predicate.
 template <int MODE, bool INTERIOR, int EB, int EB_G = EB, bool NTG = false,
-          bool GT_ALIGNED = false, bool RS = false>
+          bool GT_ALIGNED = false, bool RS = false, bool SPLIT_POS = false>
 __device__ __forceinline__ void tile_body(
     const char* __restrict__ zimg, const char* __restrict__ ztxt,
     float t, float bias, float* __restrict__ out, __bf16* __restrict__ g_out,
@@ -229,6 +261,11 @@ __device__ __forceinline__ void tile_body(
   const int wave = threadIdx.x >> 6;
   const int wrow = (wave >> 2) * 128;   // wave sub-tile origin: 2×4 grid
   const int wcol = (wave & 3) * 64;
+  // Where the bf16 LDS-staged g writeback is compiled in (g_lds16 below) the
+  // MFMA operands are exchanged so a lane's 4 regs are 4 consecutive columns
+  // of one g row: two packed converts + one ds_write_b64 per fragment.
+  constexpr bool SWAP =
+      (MODE != 0) && (EB == 2) && (EB_G == 2) && INTERIOR && GT_ALIGNED;
 
   f32x4 acc[FM][FN];
 #pragma unroll
@@ -328,7 +365,7 @@ __device__ __forceinline__ void tile_body(
           asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
         }
         __builtin_amdgcn_s_setprio(1);
-        mma_half_bf16(smem, aAddr[0], bAddr[0], acc);
+        mma_half_bf16<SWAP>(smem, aAddr[0], bAddr[0], acc);
         __builtin_amdgcn_s_setprio(0);
         if (more) {
           stage_half((kt + 1) & 1, 1);
@@ -338,7 +375,7 @@ __device__ __forceinline__ void tile_body(
           asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         }
         __builtin_amdgcn_s_setprio(1);
-        mma_half_bf16(smem, aAddr[1], bAddr[1], acc);
+        mma_half_bf16<SWAP>(smem, aAddr[1], bAddr[1], acc);
         __builtin_amdgcn_s_setprio(0);
         aAddr[0] ^= 2 * TILE_BYTES; aAddr[1] ^= 2 * TILE_BYTES;
         bAddr[0] ^= 2 * TILE_BYTES; bAddr[1] ^= 2 * TILE_BYTES;
@@ -378,8 +415,8 @@ __device__ __forceinline__ void tile_body(
                           (kt + 1) * KTE);
       }
       if (EB == 2) {
-        mma_half_bf16(smem, aAddr[0], bAddr[0], acc);
-        mma_half_bf16(smem, aAddr[1], bAddr[1], acc);
+        mma_half_bf16<SWAP>(smem, aAddr[0], bAddr[0], acc);
+        mma_half_bf16<SWAP>(smem, aAddr[1], bAddr[1], acc);
       } else {
         mma_ktile_fp8(smem, aAddr, bAddr, acc, sA, sB);
       }
@@ -397,24 +434,51 @@ __device__ __forceinline__ void tile_body(
   // MODE 0 emits only the loss; MODE 1 only g + scalar partials; MODE 2
   // ("fwd+g") all three — the whole fwd+bwd recompute collapse costs one
   // extra log and the loss adds per lane.
-  float s_loss = 0.f, s_gdot = 0.f, s_g = 0.f;
+  // With SWAP the fragment is transposed: row = lane&15, col = (lane>>4)*4
+  // + reg.  lrow/lcol are the lane's coordinates of reg 0 in a fragment.
+  //
+  // Label predicate.  A tile can hold a positive only if the diagonal
+  // segment [row_base + diag, row_base + diag + 255] meets its column range
+  // (block-uniform; DIAG_NONE tested first, the sum is 64-bit).  At the
+  // headline shape 16256 of 16384 tiles cannot: under SPLIT_POS they run a
+  // body with no compare or select at all.  Otherwise the per-element test
+  // gcol == grow + diag is one compare of the per-lane constant
+  // dl = gcol0 − grow0 − diag with a compile-time fragment offset; dl =
+  // INT_MIN (never matched, the offsets are within ±400) when the tile holds
+  // no positive.
+  const int lrow = SWAP ? (lane & 15) : (lane >> 4) * 4;
+  const int lcol = SWAP ? (lane >> 4) * 4 : (lane & 15);
+  const long long dlo = (long long)row_base + diag;
+  const bool has_pos = (diag != DIAG_NONE) && (dlo + (BM - 1) >= col_base) &&
+      (dlo <= (long long)col_base + (BN - 1));
+  const int dl = has_pos
+      ? (int)((long long)(col_base + wcol + lcol) -
+              (long long)(row_base + wrow + lrow) - diag)
+      : INT_MIN;
+  float s_relu = 0.f, s_log2 = 0.f, s_gdot = 0.f, s_g = 0.f;
   if (MODE == 0) {
+    auto body = [&](auto pc) __attribute__((always_inline)) {
+      constexpr bool POS = decltype(pc)::value;
 #pragma unroll
-    for (int mi = 0; mi < FM; ++mi) {
+      for (int mi = 0; mi < FM; ++mi) {
 #pragma unroll
-      for (int ni = 0; ni < FN; ++ni) {
+        for (int ni = 0; ni < FN; ++ni) {
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int grow = row_base + wrow + mi * 16 + (lane >> 4) * 4 + reg;
-          const int gcol = col_base + wcol + ni * 16 + (lane & 15);
-          if (INTERIOR || (grow < b && gcol < n)) {
-            const float z = acc[mi][ni][reg] * t + bias;
-            const bool pos = (diag != DIAG_NONE) && (gcol == grow + diag);
-            s_loss += softplus_f(pos ? -z : z);
+          for (int reg = 0; reg < 4; ++reg) {
+            const int grow = row_base + wrow + mi * 16 + lrow + reg;
+            const int gcol = col_base + wcol + ni * 16 + lcol;
+            if (INTERIOR || (grow < b && gcol < n)) {
+              const float z = acc[mi][ni][reg] * t + bias;
+              const bool pos = POS && (dl == mi * 16 + reg - ni * 16);
+              const float x = pos ? -z : z;
+              softplus_acc(x, __expf(-fabsf(x)), s_relu, s_log2);
+            }
           }
         }
       }
-    }
+    };
+    if (SPLIT_POS && !has_pos) body(std::false_type{});
+    else body(std::true_type{});
   } else {
     // One per-lane base offset + per-(mi,reg) scalar row offset keeps the
     // store addressing affine — per-element (size_t)grow*ldg math made the
@@ -457,12 +521,18 @@ __device__ __forceinline__ void tile_body(
     unsigned char* g_img = reinterpret_cast<unsigned char*>(smem) + 65536;
     const int g_base0 = (wrow + (lane >> 4) * 4) * 256 + wcol + (lane & 15);
     // bf16 g staging: the 256×256-element bf16 tile is exactly the whole
-    // 128-KB smem (no gᵀ slab exists in bf16 mode).  Row-quad XOR swizzle
-    // (((row>>2)&7)<<5, ≥ bit 5) keeps 16-B chunks intact and spreads the
-    // 2-B scatter writes across all banks.
-    constexpr bool g_lds16 = (EB_G == 2) && INTERIOR && GT_ALIGNED;
+    // 128-KB smem (no gᵀ slab exists in bf16 mode).  The accumulators are
+    // transposed here (SWAP), so a lane packs its 4 regs into ONE 8-B
+    // ds_write_b64 at (row lane&15, 4 columns).  The 16-B chunk index is
+    // XOR-ed with row&15: the 16 rows × 2 column quads of any half-wave
+    // fill 256 contiguous-in-bank bytes, and the dwordx4 readback still
+    // finds whole chunks.  The fragment column offset ni*32 B sits in
+    // address bits 5-6, disjoint from the lane's own bits, so it folds
+    // into the XOR as a compile-time constant.
+    constexpr bool g_lds16 = SWAP;
     char* g_img16 = smem;
-    const int g16_base0 = (wcol + (lane & 15)) * 2;
+    const int g16_base0 = (wrow + (lane & 15)) * 512 +
+        (((wcol + (lane >> 4) * 4) * 2) ^ ((lane & 15) << 4));
     if (gt_lds || g_lds16) __syncthreads();   // operand LDS reads complete
     // Row-wise policy: the saved slabs fold the OTHER side's scale ratio
     // (g slab ← text-row ratio for the dzimg GEMM, gᵀ slab ← image-row
@@ -479,80 +549,98 @@ __device__ __forceinline__ void tile_body(
                                       : 0.0f;
       }
     }
+    auto body = [&](auto pc) __attribute__((always_inline)) {
+      constexpr bool POS = decltype(pc)::value;
 #pragma unroll
-    for (int mi = 0; mi < FM; ++mi) {
-      float rav[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-      if (RS && EB_G == 1) {
-        const int r0 = row_base + wrow + mi * 16 + (lane >> 4) * 4;
+      for (int mi = 0; mi < FM; ++mi) {
+        float rav[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+        if (RS && EB_G == 1) {
+          const int r0 = row_base + wrow + mi * 16 + (lane >> 4) * 4;
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr)
-          rav[rr] = (INTERIOR || r0 + rr < b)
-              ? a_rat[(INTERIOR || r0 + rr < b) ? (r0 + rr) : 0] : 0.0f;
-      }
+          for (int rr = 0; rr < 4; ++rr)
+            rav[rr] = (INTERIOR || r0 + rr < b)
+                ? a_rat[(INTERIOR || r0 + rr < b) ? (r0 + rr) : 0] : 0.0f;
+        }
 #pragma unroll
-      for (int ni = 0; ni < FN; ++ni) {
-        unsigned packed = 0;
+        for (int ni = 0; ni < FN; ++ni) {
+          unsigned packed = 0;
+          f32x4 gv = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-          const int grow = row_base + wrow + mi * 16 + (lane >> 4) * 4 + reg;
-          const int gcol = col_base + wcol + ni * 16 + (lane & 15);
-          if (INTERIOR || (grow < b && gcol < n)) {
-            const float dot = acc[mi][ni][reg];
-            const float z = dot * t + bias;
-            const bool pos = (diag != DIAG_NONE) && (gcol == grow + diag);
-            const float x = pos ? -z : z;            // −l·z
-            const float y = __expf(-fabsf(x));
-            const float r = __builtin_amdgcn_rcpf(1.0f + y);
-            if (MODE == 2)
-              s_loss += fmaxf(x, 0.0f) + __logf(1.0f + y);
-            const float sig = (x >= 0.0f) ? r : y * r;   // σ(x)
-            const float g = pos ? -sig : sig;
-            const unsigned row_off = (unsigned)(mi * 16 + reg) * (unsigned)ldg;
-            if (EB_G == 1) {
-              const unsigned char q = __hip_fp8_e4m3(
-                  (RS ? g * rbv[ni] : g) * 448.0f).__x;
-              if (gt_lds)
-                g_img[g_base0 + (mi * 16 + reg) * 256 + ni * 16] = q;
-              else
-                st_g<NTG>(reinterpret_cast<unsigned char*>(gb)
-                              + lane_off + row_off + ni * 16, q);
-              const unsigned char qt = RS
-                  ? __hip_fp8_e4m3(g * rav[reg] * 448.0f).__x : q;
-              packed |= (unsigned)qt << (8 * reg);
-            } else if (g_lds16) {
-              const int rloc = wrow + mi * 16 + (lane >> 4) * 4 + reg;
-              *reinterpret_cast<__bf16*>(g_img16 + rloc * 512 +
-                  ((g16_base0 + ni * 32) ^ (((rloc >> 2) & 7) << 5))) =
-                  (__bf16)g;
-            } else {
-              st_g<NTG>(reinterpret_cast<__bf16*>(gb)
-                            + lane_off + row_off + ni * 16, (__bf16)g);
+          for (int reg = 0; reg < 4; ++reg) {
+            const int grow =
+                row_base + wrow + mi * 16 + lrow + (SWAP ? 0 : reg);
+            const int gcol =
+                col_base + wcol + ni * 16 + lcol + (SWAP ? reg : 0);
+            if (INTERIOR || (grow < b && gcol < n)) {
+              const float dot = acc[mi][ni][reg];
+              const float z = dot * t + bias;
+              const bool pos = POS &&
+                  (dl == mi * 16 - ni * 16 + (SWAP ? -reg : reg));
+              const float x = pos ? -z : z;            // −l·z
+              const float y = __expf(-fabsf(x));
+              const float r = __builtin_amdgcn_rcpf(1.0f + y);
+              if (MODE == 2) softplus_acc(x, y, s_relu, s_log2);
+              const float sig = (x >= 0.0f) ? r : y * r;   // σ(x)
+              const float g = pos ? -sig : sig;
+              const unsigned row_off =
+                  (unsigned)(mi * 16 + reg) * (unsigned)ldg;
+              if (EB_G == 1) {
+                const unsigned char q = __hip_fp8_e4m3(
+                    (RS ? g * rbv[ni] : g) * 448.0f).__x;
+                if (gt_lds)
+                  g_img[g_base0 + (mi * 16 + reg) * 256 + ni * 16] = q;
+                else
+                  st_g<NTG>(reinterpret_cast<unsigned char*>(gb)
+                                + lane_off + row_off + ni * 16, q);
+                const unsigned char qt = RS
+                    ? __hip_fp8_e4m3(g * rav[reg] * 448.0f).__x : q;
+                packed |= (unsigned)qt << (8 * reg);
+              } else if (g_lds16) {
+                gv[reg] = g;
+              } else {
+                st_g<NTG>(reinterpret_cast<__bf16*>(gb)
+                              + lane_off + row_off + ni * 16, (__bf16)g);
+              }
+              s_gdot += g * dot;
+              s_g += g;
             }
-            s_gdot += g * dot;
-            s_g += g;
           }
-        }
-        if (EB_G == 1) {
-          const unsigned toff = lane_off_t + (unsigned)(ni * 16) * (unsigned)b
-              + (unsigned)(mi * 16);
-          if (gt_lds) {
-            gt_img[gt_base0 + ni * 1024 +
-                   ((((wrow >> 4) + mi) ^ gsel) << 2)] = packed;
-          } else if (INTERIOR) {
-            st_g<NTG>(reinterpret_cast<unsigned*>(gtb + toff), packed);
-          } else {
-            const int grow0 = row_base + wrow + mi * 16 + (lane >> 4) * 4;
-            const int gcol = col_base + wcol + ni * 16 + (lane & 15);
-            if (gcol < n)
+          if (g_lds16) {
+            // 4 consecutive columns of row mi*16 + (lane&15): packed RNE
+            // converts (same rounding as the scalar cast), one 8-B write.
+            *reinterpret_cast<bf16x4*>(
+                g_img16 + mi * (16 * 512) + (g16_base0 ^ (ni * 32))) =
+                __builtin_convertvector(gv, bf16x4);
+          }
+          if (EB_G == 1) {
+            const unsigned toff = lane_off_t
+                + (unsigned)(ni * 16) * (unsigned)b + (unsigned)(mi * 16);
+            if (gt_lds) {
+              gt_img[gt_base0 + ni * 1024 +
+                     ((((wrow >> 4) + mi) ^ gsel) << 2)] = packed;
+            } else if (INTERIOR) {
+              st_g<NTG>(reinterpret_cast<unsigned*>(gtb + toff), packed);
+            } else {
+              const int grow0 = row_base + wrow + mi * 16 + (lane >> 4) * 4;
+              const int gcol = col_base + wcol + ni * 16 + (lane & 15);
+              if (gcol < n)
 #pragma unroll
-              for (int reg = 0; reg < 4; ++reg)
-                if (grow0 + reg < b)
-                  gtb[toff + reg] = (unsigned char)(packed >> (8 * reg));
+                for (int reg = 0; reg < 4; ++reg)
+                  if (grow0 + reg < b)
+                    gtb[toff + reg] = (unsigned char)(packed >> (8 * reg));
+            }
           }
         }
+        // Cap epilogue register pressure.  The empty asm pins the running
+        // sums here: without it the add chains were seen sunk past the
+        // writeback in the general kernel (128 addends kept live, spilled).
+        if (MODE == 2) asm volatile("" : "+v"(s_relu), "+v"(s_log2));
+        asm volatile("" : "+v"(s_gdot), "+v"(s_g));
+        __builtin_amdgcn_sched_barrier(0);
       }
-      __builtin_amdgcn_sched_barrier(0);  // cap epilogue register pressure
-    }
+    };
+    if (SPLIT_POS && !has_pos) body(std::false_type{});
+    else body(std::true_type{});
     if (g_lds16) {
       // bf16 writeback: 8192 16-B chunks (8 elements of one row each),
       // nt dwordx4; the XOR swizzle is inverted per (row, chunk).
@@ -563,7 +651,7 @@ __device__ __forceinline__ void tile_body(
         const int row = c >> 5;
         const int cs = c & 31;
         const u32x4 v = *reinterpret_cast<const u32x4*>(
-            g_img16 + row * 512 + ((cs * 16) ^ (((row >> 2) & 7) << 5)));
+            g_img16 + row * 512 + ((cs ^ (row & 15)) * 16));
         st_g<true>(reinterpret_cast<u32x4*>(
                        gb + (size_t)row * (ldg * EB_G) + cs * 16), v);
       }
@@ -591,6 +679,8 @@ __device__ __forceinline__ void tile_body(
     }
   }
 
+  // Fold the tile's log2 sum into the loss partial: one multiply by ln 2.
+  float s_loss = s_relu + LN2_F * s_log2;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     if (MODE != 1) s_loss += __shfl_down(s_loss, off);
@@ -637,9 +727,9 @@ __device__ __forceinline__ void tile_body(
   }
 }
 
-__device__ __forceinline__ void remap_block(int flags, int& bx, int& by) {
-  const int gx = gridDim.x, gy = gridDim.y;
-  int id = blockIdx.y * gx + blockIdx.x;
+// Flat tile id (0 .. gx*gy-1) → tile coordinates under the remap flags.
+__device__ __forceinline__ void remap_id(int flags, int id, int gx, int gy,
+                                         int& bx, int& by) {
   if (flags & 1) {
     const int nwg = gx * gy;
     const int q = nwg / NXCD, r = nwg % NXCD;
@@ -663,9 +753,16 @@ __device__ __forceinline__ void remap_block(int flags, int& bx, int& by) {
   }
 }
 
+__device__ __forceinline__ void remap_block(int flags, int& bx, int& by) {
+  remap_id(flags, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, gridDim.y,
+           bx, by);
+}
+
 // Interior-only kernel: every tile full, d % K-step == 0, n%8==0 — checked
 // by the host launcher.  Separate from the general kernel so the hot path's
-// register allocation is not inflated by the guarded path.
+// register allocation is not inflated by the guarded path.  Launched for
+// the fp8 and e4m3-g instantiations; bf16 with bf16 g takes the persistent
+// kernel below.
 template <int MODE, int EB, int EB_G = EB, bool NTG = false, bool RS = false>
 __launch_bounds__(THREADS) __global__ void siglip_tile_kernel_interior(
     const char* __restrict__ zimg, const char* __restrict__ ztxt,
@@ -681,7 +778,7 @@ __launch_bounds__(THREADS) __global__ void siglip_tile_kernel_interior(
   remap_block(flags, bx, by);
   const float t = __expf(*t_prime);
   const float bias = *bias_p;
-  tile_body<MODE, true, EB, EB_G, NTG, true, RS>(
+  tile_body<MODE, true, EB, EB_G, NTG, true, RS, true>(
       zimg, ztxt, t, bias, out, g_out, gt_out, a_e8, b_e8, a_rat, b_rat,
       b, n, d, ldg, diag, bx * BM, by * BN, smem);
 }
@@ -724,6 +821,296 @@ __launch_bounds__(THREADS) __global__ void siglip_tile_kernel(
     tile_body<MODE, false, EB, EB_G, NTG, false, RS>(
         zimg, ztxt, t, bias, out, g_out, gt_out, a_e8, b_e8, a_rat, b_rat,
         b, n, d, ldg, diag, row_base, col_base, smem);
+}
+
+// ---------------------------------------------------------------------------
+// Persistent bf16 interior kernel (all three MODEs; bf16 g).  Same tile, same
+// LDS operand image, same MFMA order and same per-element epilogue math as
+// tile_body's interior bf16 path, but:
+//   - workgroup w walks the flat tile ids w, w+G, w+2G, … (G = gridDim.x,
+//     each id through remap_id).  With G % 8 == 0 a tile's id % 8 is still
+//     the XCD it runs on, so the XCD-contiguous remap and the per-XCD scalar
+//     slots keep their meaning.
+//   - the K-loop is ONE stream across tiles: the last K-step of a tile
+//     stages the first K-step of the next (new base pointers) where the
+//     one-tile loop has "no more", so those granules are in flight before
+//     the epilogue starts.  The buffer parity runs on through tile
+//     boundaries (odd K-step counts flip it from tile to tile).
+//   - the g writeback stages per WAVE in the 32 KiB above the operand
+//     buffers (the kernel declares all 160 KiB): one 16-row × 128-B slice
+//     per mi, two 2-KiB slots per wave so the writeback of slice mi overlaps
+//     the math of mi+1.  A wave only reads what it wrote (LDS operations of
+//     one wave execute in order), so the epilogue has no block-wide barrier
+//     and never touches the operand buffers — which is what makes the early
+//     prefetch legal.
+//   - the scalar partials fold per tile into per-lane running sums; the wave
+//     shuffle, the cross-wave LDS reduce and the three atomics run once per
+//     WORKGROUP (adds in sequence: ≤128 per tile, ≤tiles-per-workgroup,
+//     6 shuffle, 8 waves).
+// Workgroups never wait on each other.
+//
+// vmcnt accounting.  The g stores count on the same vmcnt as the LDS-DMA
+// loads.  The counted waits below are those of the one-tile loop, derived
+// for loads alone: "at most k operations outstanding".  With stores in the
+// count, at most k outstanding still implies at most k LOADS outstanding,
+// and the loads complete in issue order among themselves (the one-tile loop
+// relies on the same), so every wait still retires the granule it names:
+// the stores can only make a wait stricter, never looser.  Nothing is
+// assumed about the completion order of stores relative to loads.  The price
+// is that the first two waits of a tile also wait for nearly all of the
+// previous tile's g stores (the newly staged loads fill most of the k).
+template <int MODE>
+__launch_bounds__(THREADS) __global__ void siglip_tile_kernel_persistent(
+    const char* __restrict__ zimg, const char* __restrict__ ztxt,
+    const float* __restrict__ t_prime, const float* __restrict__ bias_p,
+    float* __restrict__ out, __bf16* __restrict__ g_out,
+    int d, int ldg, int diag, int flags, int gx, int gy) {
+  __shared__ char smem[5 * TILE_BYTES];
+  constexpr bool SWAP = MODE != 0;     // transposed fragments, see tile_body
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wrow = (wave >> 2) * 128;
+  const int wcol = (wave & 3) * 64;
+  const float t = __expf(*t_prime);
+  const float bias = *bias_p;
+  const int ktiles = d / 64;
+  const int ntiles = gx * gy;
+  const int G = gridDim.x;
+
+  const int fr = lane & 15;
+  const int qbase = lane >> 4;
+  int aAddr[2], bAddr[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    aAddr[kk] = chunk_addr(wrow + fr, kk * 4 + qbase);
+    bAddr[kk] = TILE_BYTES + chunk_addr(wcol + fr, kk * 4 + qbase);
+  }
+
+  // DMA staging, as in tile_body.
+  const int rsub = lane >> 2;
+  const int cch = lane & 3;
+  int va[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int rloc = (wave * 2 + j) * 16 + rsub;
+    va[j] = rloc * d * 2 + ((cch ^ kmask2(rloc)) * 16);
+  }
+  const char* abase;
+  const char* bbase;
+  auto stage_half = [&](int buf, int h) {
+    const int lb = __builtin_amdgcn_readfirstlane(wave * 2048) +
+        buf * (2 * TILE_BYTES) + h * HALF_BYTES;
+    const int hoff = h * 64;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      __builtin_amdgcn_global_load_lds(
+          (gas_ptr)(abase + hoff + va[j]),
+          (las_ptr)(smem + lb + j * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(
+          (gas_ptr)(bbase + hoff + va[j]),
+          (las_ptr)(smem + lb + TILE_BYTES + j * 1024), 16, 0, 0);
+    }
+  };
+
+  // Per-wave g staging: slot s of this wave at stg + s*2048, row r at
+  // r*128, 16-B chunk c at (c ^ ((r>>1)&7))*16 — rows r, r+1 (r even) share
+  // a mask and fill one 256-B bank row, so the 16 rows × 2 column quads of a
+  // half-wave's 8-B writes and the 2 rows × 8 chunks of a quarter-wave's
+  // 16-B reads are conflict-free.  Write: lane holds row lane&15, columns
+  // ni*16 + (lane>>4)*4 .. +3 → chunk ni*2 + (lane>>5), half (lane>>4)&1;
+  // ni sits in chunk bits 1-2 and folds into the XOR as a constant.  Read /
+  // store: 16-B unit u = j*64 + lane → row u>>3, chunk u&7.
+  char* stg = smem + 4 * TILE_BYTES + wave * 4096;
+  const int wr0 = fr * 128 + (((lane >> 5) ^ ((fr >> 1) & 7)) << 4) +
+      ((lane >> 4) & 1) * 8;
+  int rd[2];
+  unsigned goff[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int u = j * 64 + lane;
+    const int r = u >> 3, c = u & 7;
+    rd[j] = r * 128 + ((c ^ ((r >> 1) & 7)) << 4);
+    goff[j] = ((unsigned)(wrow + r) * (unsigned)ldg + (unsigned)wcol) * 2u +
+        (unsigned)c * 16u;
+  }
+
+  const int lrow = SWAP ? fr : qbase * 4;
+  const int lcol = SWAP ? qbase * 4 : fr;
+
+  int tile = blockIdx.x;
+  int bx, by;
+  remap_id(flags, tile, gx, gy, bx, by);
+  int row_base = bx * BM, col_base = by * BN;
+  abase = zimg + (size_t)row_base * d * 2;
+  bbase = ztxt + (size_t)col_base * d * 2;
+  stage_half(0, 0);
+  stage_half(0, 1);
+  abase += 128; bbase += 128;
+  int nbuf = 1;                       // buffer the next K-step is staged to
+
+  float w_loss = 0.f, w_gdot = 0.f, w_g = 0.f;   // per-workgroup running sums
+  for (;;) {
+    const int next = tile + G;
+    const bool has_next = next < ntiles;
+    int nrow = 0, ncol = 0;
+    if (has_next) {
+      remap_id(flags, next, gx, gy, bx, by);
+      nrow = bx * BM; ncol = by * BN;
+    }
+
+    f32x4 acc[FM][FN];
+#pragma unroll
+    for (int mi = 0; mi < FM; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < FN; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int kt = 0; kt < ktiles; ++kt) {
+      const bool last = kt + 1 == ktiles;
+      const bool more = !last || has_next;
+      if (last && has_next) {          // next K-step = first of the next tile
+        abase = zimg + (size_t)nrow * d * 2;
+        bbase = ztxt + (size_t)ncol * d * 2;
+      }
+      if (more) {
+        stage_half(nbuf, 0);
+        // loads outstanding: h0(kt) h1(kt) h0(kt+1) = 12; ≤ 8 outstanding
+        // in all ⇒ ≤ 8 loads ⇒ h0(kt) retired (stores only tighten this).
+        asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+      } else {
+        // h0(kt) h1(kt) = 8 loads; ≤ 4 outstanding ⇒ h0(kt) retired.
+        asm volatile("s_waitcnt vmcnt(4)\n\ts_barrier" ::: "memory");
+      }
+      __builtin_amdgcn_s_setprio(1);
+      mma_half_bf16<SWAP>(smem, aAddr[0], bAddr[0], acc);
+      __builtin_amdgcn_s_setprio(0);
+      if (more) {
+        stage_half(nbuf, 1);
+        abase += 128; bbase += 128;
+        // loads outstanding: h1(kt) h0(kt+1) h1(kt+1) = 12; ≤ 8 ⇒ h1(kt)
+        // retired.
+        asm volatile("s_waitcnt vmcnt(8)\n\ts_barrier" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+      }
+      __builtin_amdgcn_s_setprio(1);
+      mma_half_bf16<SWAP>(smem, aAddr[1], bAddr[1], acc);
+      __builtin_amdgcn_s_setprio(0);
+      aAddr[0] ^= 2 * TILE_BYTES; aAddr[1] ^= 2 * TILE_BYTES;
+      bAddr[0] ^= 2 * TILE_BYTES; bAddr[1] ^= 2 * TILE_BYTES;
+      nbuf ^= 1;
+      // Buffer reuse is fenced exactly as in the one-tile loop: the
+      // epilogue adds no barrier and touches no operand buffer.
+    }
+
+    // Epilogue (see tile_body for the math and the label predicate).
+    const long long dlo = (long long)row_base + diag;
+    const bool has_pos = (diag != DIAG_NONE) &&
+        (dlo + (BM - 1) >= col_base) &&
+        (dlo <= (long long)col_base + (BN - 1));
+    const int dl = has_pos
+        ? (int)((long long)(col_base + wcol + lcol) -
+                (long long)(row_base + wrow + lrow) - diag)
+        : INT_MIN;
+    float s_relu = 0.f, s_log2 = 0.f, s_gdot = 0.f, s_g = 0.f;
+    char* gb = reinterpret_cast<char*>(g_out) +
+        ((size_t)row_base * ldg + col_base) * 2;
+    auto body = [&](auto pc) __attribute__((always_inline)) {
+      constexpr bool POS = decltype(pc)::value;
+      u32x4 pend[2];
+      auto store_slice = [&](int m) __attribute__((always_inline)) {
+        char* gbm = gb + (size_t)(m * 16) * ((size_t)ldg * 2);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          st_g<true>(reinterpret_cast<u32x4*>(gbm + goff[j]), pend[j]);
+      };
+#pragma unroll
+      for (int mi = 0; mi < FM; ++mi) {
+        char* slot = stg + (mi & 1) * 2048;
+#pragma unroll
+        for (int ni = 0; ni < FN; ++ni) {
+          f32x4 gv = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            const float dot = acc[mi][ni][reg];
+            const float z = dot * t + bias;
+            const bool pos = POS &&
+                (dl == mi * 16 - ni * 16 + (SWAP ? -reg : reg));
+            const float x = pos ? -z : z;            // −l·z
+            const float y = __expf(-fabsf(x));
+            if (MODE != 1) softplus_acc(x, y, s_relu, s_log2);
+            if (MODE != 0) {
+              const float r = __builtin_amdgcn_rcpf(1.0f + y);
+              const float sig = (x >= 0.0f) ? r : y * r;   // σ(x)
+              const float g = pos ? -sig : sig;
+              gv[reg] = g;
+              s_gdot += g * dot;
+              s_g += g;
+            }
+          }
+          if (MODE != 0)
+            *reinterpret_cast<bf16x4*>(slot + (wr0 ^ (ni * 32))) =
+                __builtin_convertvector(gv, bf16x4);
+        }
+        if (MODE != 0) {
+          // Store slice mi-1 (read back one iteration ago, so its LDS
+          // latency hid under this slice's math), then read this slice
+          // back as whole 128-B rows: the wave reads only what it wrote.
+          if (mi > 0) store_slice(mi - 1);
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            pend[j] = *reinterpret_cast<const u32x4*>(slot + rd[j]);
+          if (mi == FM - 1) store_slice(mi);
+          asm volatile("" : "+v"(s_gdot), "+v"(s_g));
+        }
+        if (MODE != 1) asm volatile("" : "+v"(s_relu), "+v"(s_log2));
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    if (!has_pos) body(std::false_type{});
+    else body(std::true_type{});
+    w_loss += s_relu + LN2_F * s_log2;
+    w_gdot += s_gdot;
+    w_g += s_g;
+
+    if (!has_next) break;
+    tile = next; row_base = nrow; col_base = ncol;
+  }
+
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    if (MODE != 1) w_loss += __shfl_down(w_loss, off);
+    if (MODE != 0) {
+      w_gdot += __shfl_down(w_gdot, off);
+      w_g += __shfl_down(w_g, off);
+    }
+  }
+  // Once per workgroup: cross-wave reduce in the staging region (no DMA is
+  // in flight after the last tile's vmcnt(0)), one atomic per scalar into
+  // the workgroup's XCD slot.
+  __syncthreads();
+  float* red = reinterpret_cast<float*>(smem + 4 * TILE_BYTES);
+  if (lane == 0) {
+    red[wave] = w_loss;
+    red[8 + wave] = w_gdot;
+    red[16 + wave] = w_g;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float r_loss = 0.f, r_gdot = 0.f, r_g = 0.f;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+      r_loss += red[w];
+      r_gdot += red[8 + w];
+      r_g += red[16 + w];
+    }
+    const int slot = (blockIdx.x & (NXCD - 1)) * OUT_STRIDE;
+    if (MODE != 1) atomicAdd(&out[slot + 0], r_loss);
+    if (MODE != 0) {
+      atomicAdd(&out[slot + 1], r_gdot);
+      atomicAdd(&out[slot + 2], r_g);
+    }
+  }
 }
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -810,7 +1197,36 @@ int launch_nt(uintptr_t stream, const void* zimg, const void* ztxt,
   const bool interior = (b % BM == 0) && (n % BN == 0) &&
       (d % (128 / EB) == 0) &&
       (EB_G == 1 ? (ldg & 15) == 0 : (MODE == 0 || (ldg & 7) == 0));
-  if (interior)
+  if constexpr (EB == 2 && EB_G == 2) {
+    if (interior) {
+      // Persistent grid: min(tiles, CUs) workgroups (one fits per CU: 160 KiB
+      // LDS), rounded down to a multiple of 8 above 8 so that tile id % 8
+      // stays the XCD.  flags bits 8-23: workgroup cap (0 = automatic, for
+      // tests and sweeps); bit 24: one tile per workgroup, same kernel (A/B).
+      static int n_cu = 0;
+      if (n_cu == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount,
+                                  dev) != hipSuccess || n_cu <= 0)
+          return (int)hipErrorInvalidDevice;
+      }
+      const int tiles = (int)(grid.x * grid.y);
+      const int cap = (flags >> 8) & 0xffff;
+      int wgs = tiles;
+      if (!(flags & (1 << 24))) {
+        wgs = cap ? cap : n_cu;
+        if (wgs > tiles) wgs = tiles;
+        if (wgs > 8) wgs -= wgs % 8;
+      }
+      hipLaunchKernelGGL(
+          (siglip_tile_kernel_persistent<MODE>), dim3(wgs), dim3(THREADS), 0,
+          (hipStream_t)stream, (const char*)zimg, (const char*)ztxt,
+          (const float*)t_prime, (const float*)bias, (float*)out,
+          (__bf16*)g_out, d, ldg, diag, flags, (int)grid.x, (int)grid.y);
+      return (int)hipGetLastError();
+    }
+  } else if (interior) {
     hipLaunchKernelGGL(
         (siglip_tile_kernel_interior<MODE, EB, EB_G, NTG, RS>),
         grid, dim3(THREADS), 0, (hipStream_t)stream,
@@ -820,16 +1236,17 @@ int launch_nt(uintptr_t stream, const void* zimg, const void* ztxt,
         (const unsigned char*)a_e8, (const unsigned char*)b_e8,
         (const float*)a_rat, (const float*)b_rat,
         b, n, d, ldg, diag, flags);
-  else
-    hipLaunchKernelGGL(
-        (siglip_tile_kernel<MODE, EB, EB_G, NTG, RS>), grid, dim3(THREADS),
-        0, (hipStream_t)stream,
-        (const char*)zimg, (const char*)ztxt,
-        (const float*)t_prime, (const float*)bias,
-        (float*)out, (__bf16*)g_out, (unsigned char*)gt_out,
-        (const unsigned char*)a_e8, (const unsigned char*)b_e8,
-        (const float*)a_rat, (const float*)b_rat,
-        b, n, d, ldg, diag, flags);
+    return (int)hipGetLastError();
+  }
+  hipLaunchKernelGGL(
+      (siglip_tile_kernel<MODE, EB, EB_G, NTG, RS>), grid, dim3(THREADS),
+      0, (hipStream_t)stream,
+      (const char*)zimg, (const char*)ztxt,
+      (const float*)t_prime, (const float*)bias,
+      (float*)out, (__bf16*)g_out, (unsigned char*)gt_out,
+      (const unsigned char*)a_e8, (const unsigned char*)b_e8,
+      (const float*)a_rat, (const float*)b_rat,
+      b, n, d, ldg, diag, flags);
   return (int)hipGetLastError();
 }
 
@@ -861,7 +1278,7 @@ int launch(uintptr_t stream, const void* zimg, const void* ztxt,
 
 extern "C" {
 
-int siglip_ext_abi(void) { return 11; }
+int siglip_ext_abi(void) { return 12; }
 
 // Fused per-tensor fp8-e4m3 quantization: one amax pass (block reduce +
 // one atomicMax of the float bits per block — positive floats order as

@@ -15,6 +15,9 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
 - ``ops`` — hand-written CDNA4 HIP kernels (MFMA, LDS-tiled, gfx950) fusing
   pairwise logits + temperature/bias + log-sigmoid + reduction, forward and
   backward, never materializing the full N×N logits matrix.
+- ``retrieval_ranks`` / ``recall_at_k`` / ``distributed_retrieval_ranks`` —
+  the retrieval rank of every matching pair in both directions, counted by a
+  fused HIP kernel over the same never-materialized grid.
 
 The compute path is PyTorch-ROCm + HIP/CDNA4 kernels + RCCL over xGMI; there
 are no CUDA compatibility layers and no multi-backend dispatch.
@@ -24,6 +27,14 @@ __version__ = "0.2.0"
 
 from .losses.sigmoid_loss import DistributedSigmoidLoss, SigLipLoss
 from .losses.functional import sigmoid_contrastive_loss
+from .losses.retrieval import (
+    RetrievalRanks,
+    pair_rank_counts,
+    positive_scores,
+    retrieval_ranks,
+    recall_at_k,
+    distributed_retrieval_ranks,
+)
 from .parallel.ring import (
     neighbour_exchange,
     neighbour_exchange_bidir,
@@ -36,6 +47,12 @@ __all__ = [
     "DistributedSigmoidLoss",
     "SigLipLoss",
     "sigmoid_contrastive_loss",
+    "RetrievalRanks",
+    "pair_rank_counts",
+    "positive_scores",
+    "retrieval_ranks",
+    "recall_at_k",
+    "distributed_retrieval_ranks",
     "neighbour_exchange",
     "neighbour_exchange_bidir",
     "neighbour_exchange_with_grad",

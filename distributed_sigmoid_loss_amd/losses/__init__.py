@@ -1,4 +1,14 @@
 from .sigmoid_loss import DistributedSigmoidLoss, SigLipLoss
 from .functional import sigmoid_contrastive_loss
+from .retrieval import (
+    RetrievalRanks,
+    pair_rank_counts,
+    positive_scores,
+    retrieval_ranks,
+    recall_at_k,
+    distributed_retrieval_ranks,
+)
 
-__all__ = ["DistributedSigmoidLoss", "SigLipLoss", "sigmoid_contrastive_loss"]
+__all__ = ["DistributedSigmoidLoss", "SigLipLoss", "sigmoid_contrastive_loss",
+           "RetrievalRanks", "pair_rank_counts", "positive_scores",
+           "retrieval_ranks", "recall_at_k", "distributed_retrieval_ranks"]

@@ -23,6 +23,10 @@ exposes:
   deterministic two-stage reduction), wired into the projection towers by
   :func:`linear_nobias`; :func:`scale_bf16_` (in-place vectorized scale of
   the saved-g gradient products).
+- retrieval metrics: :func:`pair_rank_counts` — per-row and per-column
+  counts of the scores above a threshold, a second (integer) reduction over
+  the same never-materialized pair grid (``losses/retrieval.py`` turns them
+  into ranks and recall@k).
 
 Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
@@ -148,9 +152,9 @@ def _load():
         _lib_err = f"failed to load {SO_PATH}: {e}"
         return None
     lib.siglip_ext_abi.restype = ctypes.c_int
-    if lib.siglip_ext_abi() != 12:
+    if lib.siglip_ext_abi() != 13:
         _lib_err = (f"stale HIP extension at {SO_PATH} "
-                    f"(ABI {lib.siglip_ext_abi()}, need 12); rebuild with: "
+                    f"(ABI {lib.siglip_ext_abi()}, need 13); rebuild with: "
                     "python -m distributed_sigmoid_loss_amd.ops.build --force")
         return None
     # (stream, mode, eb, eb_g, 11 pointers, b, n, d, ldg, diag, flags)
@@ -178,6 +182,10 @@ def _load():
     lib.scale_bf16_inplace.restype = ctypes.c_int
     lib.scale_bf16_inplace.argtypes = (
         [ctypes.c_void_p] * 3 + [ctypes.c_longlong])
+    # (stream, zimg, ztxt, row_thr, col_thr, row_cnt, col_cnt, b, n, d, diag)
+    lib.pair_rank_counts_bf16.restype = ctypes.c_int
+    lib.pair_rank_counts_bf16.argtypes = (
+        [ctypes.c_void_p] * 7 + [ctypes.c_int] * 4)
     _lib = lib
     return _lib
 
@@ -867,6 +875,75 @@ def siglip_fwd_g(zimg: torch.Tensor, ztxt: torch.Tensor,
     _launch_tile(2, quant, zi_k, zt_k, tp_k, _prep_scalar(bias, dev), out3,
                  g=g, gt=gt, diag_offset=diag_offset, rowscales=rowscales)
     return out3, g_slab, gt_slab if fp8g else None
+
+
+def _rank_side(name: str, thr, cnt, length: int, device):
+    """Validate one side (rows or columns) of :func:`pair_rank_counts`;
+    returns ``(thr, cnt)`` with ``cnt`` allocated if needed, or
+    ``(None, None)`` for a skipped side."""
+    if thr is None:
+        if cnt is not None:
+            raise RuntimeError(f"{name}_cnt given without {name}_thr")
+        return None, None
+    if (thr.device != device or thr.dtype != torch.float32
+            or thr.shape != (length,) or not thr.is_contiguous()):
+        raise RuntimeError(
+            f"{name}_thr must be a contiguous fp32 ({length},) tensor on "
+            f"{device} (got {thr.dtype} {tuple(thr.shape)} on {thr.device})")
+    if cnt is None:
+        cnt = torch.zeros(length, device=device, dtype=torch.int32)
+    elif (cnt.device != device or cnt.dtype != torch.int32
+          or cnt.shape != (length,) or not cnt.is_contiguous()):
+        raise RuntimeError(
+            f"{name}_cnt must be a contiguous int32 ({length},) tensor on "
+            f"{device} (got {cnt.dtype} {tuple(cnt.shape)} on {cnt.device})")
+    return thr, cnt
+
+
+def pair_rank_counts(zimg: torch.Tensor, ztxt: torch.Tensor,
+                     row_thr: Optional[torch.Tensor] = None,
+                     col_thr: Optional[torch.Tensor] = None,
+                     diag_offset: Optional[int] = None,
+                     row_cnt: Optional[torch.Tensor] = None,
+                     col_cnt: Optional[torch.Tensor] = None):
+    """Threshold counts over the ``(b, n)`` score grid ``s = zimg @ ztxtᵀ``
+    without materializing it → ``(row_cnt | None, col_cnt | None)``:
+
+    ``row_cnt[i] += #{j ≠ i + diag_offset : s_ij > row_thr[i]}`` and
+    ``col_cnt[j] += #{i ≠ j − diag_offset : s_ij > col_thr[j]}`` (strict
+    ``>``; ``diag_offset=None``: nothing is excluded).  Thresholds are fp32
+    ``(b,)`` / ``(n,)``; a side without a threshold is skipped and returned
+    as ``None``.  Counts are int32 and ADDED into ``row_cnt`` / ``col_cnt``
+    when given (the caller zeroes them), so column chunks (``ztxt[j0:j1]``
+    with ``diag_offset − j0``) and repeated calls accumulate; otherwise they
+    start from zeros allocated here.  Integer atomics only: the result is
+    bitwise reproducible.  No autograd."""
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings, got "
+            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
+    _validate(zimg, ztxt, "bf16")
+    if ztxt.device != zimg.device:
+        raise RuntimeError("zimg and ztxt must be on the same device")
+    b, d = zimg.shape
+    n = ztxt.shape[0]
+    if b < 1 or n < 1:
+        raise RuntimeError("pair_rank_counts needs a non-empty block")
+    lib = _require_lib()
+    zi, zt = zimg.detach().contiguous(), ztxt.detach().contiguous()
+    row_thr, row_cnt = _rank_side("row", row_thr, row_cnt, b, zi.device)
+    col_thr, col_cnt = _rank_side("col", col_thr, col_cnt, n, zi.device)
+    if row_thr is None and col_thr is None:
+        return None, None
+    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
+    if not -(2 ** 31) < diag < 2 ** 31:
+        diag = _DIAG_NONE       # no positive can lie inside an int32 block
+    stream = torch.cuda.current_stream(zi.device).cuda_stream
+    _check(lib.pair_rank_counts_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(row_thr),
+        _ptr(col_thr), _ptr(row_cnt), _ptr(col_cnt), b, n, d, diag),
+        "pair_rank_counts_bf16")
+    return row_cnt, col_cnt
 
 
 class _FusedL2Normalize(torch.autograd.Function):

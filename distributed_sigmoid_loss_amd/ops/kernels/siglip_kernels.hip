@@ -1278,7 +1278,7 @@ int launch(uintptr_t stream, const void* zimg, const void* ztxt,
 
 extern "C" {
 
-int siglip_ext_abi(void) { return 12; }
+int siglip_ext_abi(void) { return 13; }
 
 // Fused per-tensor fp8-e4m3 quantization: one amax pass (block reduce +
 // one atomicMax of the float bits per block — positive floats order as

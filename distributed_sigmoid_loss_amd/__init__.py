@@ -18,6 +18,10 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
 - ``retrieval_ranks`` / ``recall_at_k`` / ``distributed_retrieval_ranks`` —
   the retrieval rank of every matching pair in both directions, counted by a
   fused HIP kernel over the same never-materialized grid.
+- ``DistributedSoftmaxLoss`` / ``softmax_contrastive_loss`` — the softmax
+  (CLIP / InfoNCE) baseline with the same contract: fused row and column
+  log-sum-exp forward, fused dL/dlogit backward, single device or one grid
+  across ranks.
 
 The compute path is PyTorch-ROCm + HIP/CDNA4 kernels + RCCL over xGMI; there
 are no CUDA compatibility layers and no multi-backend dispatch.
@@ -34,6 +38,10 @@ from .losses.retrieval import (
     retrieval_ranks,
     recall_at_k,
     distributed_retrieval_ranks,
+)
+from .losses.softmax_loss import (
+    DistributedSoftmaxLoss,
+    softmax_contrastive_loss,
 )
 from .parallel.ring import (
     neighbour_exchange,
@@ -53,6 +61,8 @@ __all__ = [
     "retrieval_ranks",
     "recall_at_k",
     "distributed_retrieval_ranks",
+    "DistributedSoftmaxLoss",
+    "softmax_contrastive_loss",
     "neighbour_exchange",
     "neighbour_exchange_bidir",
     "neighbour_exchange_with_grad",

@@ -8,7 +8,9 @@ from .retrieval import (
     recall_at_k,
     distributed_retrieval_ranks,
 )
+from .softmax_loss import DistributedSoftmaxLoss, softmax_contrastive_loss
 
 __all__ = ["DistributedSigmoidLoss", "SigLipLoss", "sigmoid_contrastive_loss",
            "RetrievalRanks", "pair_rank_counts", "positive_scores",
-           "retrieval_ranks", "recall_at_k", "distributed_retrieval_ranks"]
+           "retrieval_ranks", "recall_at_k", "distributed_retrieval_ranks",
+           "DistributedSoftmaxLoss", "softmax_contrastive_loss"]

@@ -1,0 +1,320 @@
+"""Softmax (InfoNCE / CLIP) contrastive loss over the image×text pair grid.
+
+The baseline the sigmoid loss is defined against, with the same contract as
+``sigmoid_contrastive_loss``: a ``(b, n)`` block ``zimg (b, d)`` × ``ztxt
+(n, d)`` whose logits never reach memory on the GPU path.
+
+    z_ij      = t · <zimg_i, ztxt_j>,   t = exp(t_prime)      (no bias: it
+                                                 cancels in a softmax)
+    row_lse_i = log Σ_j exp(z_ij)       col_lse_j = log Σ_i exp(z_ij)
+    total     = Σ_{i with a positive} (row_lse_i − z_{i,pos})
+              + Σ_{j with a positive} (col_lse_j − z_{pos,j})
+
+The positive of row ``i`` is column ``i + diag_offset``, the positive of
+column ``j`` is row ``j − diag_offset``; a row or column whose positive lies
+outside the block contributes nothing.  ``total`` is in sum form — the
+caller normalises (``total / (2 b)`` is the symmetric CLIP loss).
+
+Backward, with upstream weights ``row_w (b,)`` and ``col_w (n,)`` (zero
+where there is no positive):
+
+    g_ij  = row_w_i·exp(z_ij − row_lse_i) + col_w_j·exp(z_ij − col_lse_j)
+            − [j == i + diag_offset]·(row_w_i + col_w_j)
+    dzimg = t · g @ ztxt     dztxt = t · gᵀ @ zimg     dt' = t · Σ g_ij·s_ij
+
+with ``s = z / t``.  Forward keeps the inputs and the two LSE vectors —
+``O(b + n)``; backward recomputes the logits tile by tile and emits ``g`` as
+a bf16 slab (whole, or per column band) for the two gradient GEMMs.
+
+On GPU both passes are HIP kernels (``ops.pair_lse``, ``ops.softmax_g``);
+elsewhere a row-chunked torch composite with the same contract runs (fp32
+compute, fp64 for fp64 inputs) — the CPU path and the tests' reference.
+
+Distributed (``group``): the one-grid form.  This rank holds ``b`` image
+rows and all ``n = W·b`` text columns (``diag_offset = rank·b``).  Row LSEs
+are complete locally; column LSEs are all-gathered and folded, identical on
+every rank.  A rank's ``total`` counts its rows and the columns whose
+positive row it holds.  In backward the ranks' ``grad_output`` scalars are
+all-gathered: ``row_w = go_rank`` and ``col_w_j = go_owner(j)``, because
+``col_lse_j`` belongs to its owner's loss — the exact gradient of
+``Σ_q go_q·loss_q`` for unequal ``go_q`` too.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+import torch.nn as nn
+import torch.distributed as dist
+
+from ..parallel.collectives import all_gather_with_grad
+from .retrieval import (
+    _TORCH_ROW_CHUNK,
+    _compute_dtype,
+    _positive_rows,
+    positive_scores,
+)
+
+
+def _torch_pair_lse(zimg, ztxt, t_prime, rows=True, cols=True,
+                    row_chunk=_TORCH_ROW_CHUNK):
+    """``ops.pair_lse`` as a row-chunked torch composite: holds
+    ``O(row_chunk · n)`` logits at a time."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    dev, cdt = zimg.device, _compute_dtype(zimg)
+    t = t_prime.detach().to(device=dev, dtype=cdt).exp()
+    zt = ztxt.detach().to(cdt)
+    row_lse = torch.empty(b, device=dev, dtype=cdt) if rows else None
+    col_lse = (torch.full((n,), -math.inf, device=dev, dtype=cdt)
+               if cols else None)
+    for r0 in range(0, b, row_chunk):
+        r1 = min(b, r0 + row_chunk)
+        z = (zimg[r0:r1].detach().to(cdt) @ zt.T) * t
+        if rows:
+            row_lse[r0:r1] = torch.logsumexp(z, dim=1)
+        if cols:
+            col_lse = torch.logaddexp(col_lse, torch.logsumexp(z, dim=0))
+    return row_lse, col_lse
+
+
+def _torch_softmax_g(zimg, ztxt, t_prime, row_lse, row_w, col_lse, col_w,
+                     diag_offset, g=None, row_chunk=_TORCH_ROW_CHUNK):
+    """``ops.softmax_g`` as a row-chunked torch composite; ``g`` is in the
+    compute dtype and ``gs_partials`` has one entry."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    dev, cdt = zimg.device, _compute_dtype(zimg)
+    t = t_prime.detach().to(device=dev, dtype=cdt).exp()
+    zt = ztxt.detach().to(cdt)
+    if g is None:
+        g = torch.empty((b, n), device=dev, dtype=cdt)
+    gs = torch.zeros((), device=dev, dtype=torch.float64)
+    cols = torch.arange(n, device=dev)
+    for r0 in range(0, b, row_chunk):
+        r1 = min(b, r0 + row_chunk)
+        s = zimg[r0:r1].detach().to(cdt) @ zt.T
+        z = s * t
+        gv = torch.zeros_like(z)
+        w = torch.zeros_like(z)
+        if row_lse is not None:
+            gv += row_w[r0:r1, None] * torch.exp(z - row_lse[r0:r1, None])
+            w += row_w[r0:r1, None]
+        if col_lse is not None:
+            gv += col_w[None, :] * torch.exp(z - col_lse[None, :])
+            w += col_w[None, :]
+        if diag_offset is not None:
+            pos = torch.arange(r0, r1, device=dev) + int(diag_offset)
+            gv -= w * (cols[None, :] == pos[:, None])
+        g[r0:r1] = gv
+        gs += (gv * s).double().sum()
+    return g, gs.reshape(1)
+
+
+def _is_distributed(group) -> bool:
+    return (group is not None and dist.is_available()
+            and dist.is_initialized() and dist.get_world_size(group) > 1)
+
+
+class _SoftmaxLoss(torch.autograd.Function):
+    """Both implementations: ``hip`` runs the fused kernels and the library
+    gradient GEMMs, ``torch`` the composites above; the chunking, the
+    collectives and the weights are shared."""
+
+    @staticmethod
+    def forward(ctx, zimg, ztxt, t_prime, diag_offset, col_chunk, impl,
+                group):
+        hip = impl == "hip"
+        if hip:
+            from .. import ops
+            lse_fn = ops.pair_lse
+        else:
+            lse_fn = _torch_pair_lse
+        zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
+        b, n = zimg.shape[0], ztxt.shape[0]
+        step = int(col_chunk) if col_chunk and col_chunk > 0 else n
+        row_lse, col_parts = None, []
+        for j0 in range(0, n, step):
+            rl, cl = lse_fn(zimg, ztxt[j0:min(j0 + step, n)], t_prime)
+            row_lse = rl if row_lse is None else torch.logaddexp(row_lse, rl)
+            col_parts.append(cl)
+        col_lse = col_parts[0] if len(col_parts) == 1 else torch.cat(col_parts)
+        if group is not None:
+            # This rank's rows are a share of every column: gather the
+            # shares and fold them in rank order, the same on every rank.
+            shares = torch.empty(dist.get_world_size(group) * n,
+                                 device=col_lse.device, dtype=col_lse.dtype)
+            dist.all_gather_into_tensor(shares, col_lse.contiguous(),
+                                        group=group)
+            col_lse = torch.logsumexp(shares.view(-1, n), dim=0)
+        rows, cols = _positive_rows(b, n, diag_offset, zimg.device)
+        t = t_prime.detach().to(device=zimg.device, dtype=row_lse.dtype).exp()
+        z_pos = positive_scores(zimg, ztxt, diag_offset)[rows] * t
+        total = (row_lse[rows].double() + col_lse[cols].double()
+                 - 2.0 * z_pos.double()).sum().to(row_lse.dtype)
+        ctx.save_for_backward(zimg, ztxt, t_prime, row_lse, col_lse)
+        ctx.diag_offset, ctx.col_chunk = diag_offset, col_chunk
+        ctx.hip, ctx.group = hip, group
+        return total
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        zimg, ztxt, t_prime, row_lse, col_lse = ctx.saved_tensors
+        diag_offset, col_chunk = ctx.diag_offset, ctx.col_chunk
+        b, n = zimg.shape[0], ztxt.shape[0]
+        dev, cdt = zimg.device, row_lse.dtype
+        go = grad_output.detach().reshape(()).to(device=dev, dtype=cdt)
+        rows, cols = _positive_rows(b, n, diag_offset, dev)
+        row_w = torch.zeros(b, device=dev, dtype=cdt)
+        row_w[rows] = go
+        if ctx.group is not None:
+            # Column j's LSE term is part of the loss of the rank that holds
+            # row j − diag_offset, i.e. rank j // b.
+            go_all = torch.empty(dist.get_world_size(ctx.group), device=dev,
+                                 dtype=cdt)
+            dist.all_gather_into_tensor(go_all, go.reshape(1),
+                                        group=ctx.group)
+            col_w = go_all.repeat_interleave(b)
+        else:
+            col_w = torch.zeros(n, device=dev, dtype=cdt)
+            col_w[cols] = go
+        t = t_prime.detach().to(device=dev, dtype=cdt).exp()
+        gs_parts = []
+
+        if ctx.hip:
+            from .. import ops
+            whole = col_chunk is None and b * n * 2 < 2 ** 32
+            step = n if whole else (int(col_chunk) if col_chunk
+                                    else ops.banded_col_step(b))
+
+            def band(j0, j1, buf):
+                g, gs = ops.softmax_g(
+                    zimg, ztxt[j0:j1], t_prime, row_lse, row_w,
+                    col_lse[j0:j1].contiguous(), col_w[j0:j1].contiguous(),
+                    None if diag_offset is None else int(diag_offset) - j0,
+                    g=buf)
+                gs_parts.append(gs)
+                return ops.GBand(g, None, ztxt[j0:j1])
+
+            def bands():
+                # One reused slab: grad_gemms consumes each band before it
+                # asks for the next, so the stream orders kernel after GEMMs.
+                buf = torch.empty((b, step), device=dev,
+                                  dtype=torch.bfloat16)
+                for j0 in range(0, n, step):
+                    j1 = min(j0 + step, n)
+                    yield band(j0, j1, buf if j1 - j0 == step else None)
+
+            dzimg, dztxt = ops.grad_gemms(
+                band(0, n, None) if step >= n else bands(), zimg, n, t)
+        else:
+            step = int(col_chunk) if col_chunk and col_chunk > 0 else n
+            zi = zimg.to(cdt)
+            dzimg = torch.zeros((b, zimg.shape[1]), device=dev, dtype=cdt)
+            dztxt = torch.empty((n, zimg.shape[1]), device=dev, dtype=cdt)
+            for j0 in range(0, n, step):
+                j1 = min(j0 + step, n)
+                g, gs = _torch_softmax_g(
+                    zimg, ztxt[j0:j1], t_prime, row_lse, row_w,
+                    col_lse[j0:j1], col_w[j0:j1],
+                    None if diag_offset is None else int(diag_offset) - j0)
+                gs_parts.append(gs)
+                dzimg += g @ ztxt[j0:j1].to(cdt)
+                dztxt[j0:j1] = g.T @ zi
+            dzimg, dztxt = (dzimg * t).to(zimg.dtype), (dztxt * t).to(
+                ztxt.dtype)
+        dt = t.double() * torch.cat(gs_parts).double().sum()
+        return (dzimg, dztxt,
+                dt.to(device=t_prime.device,
+                      dtype=t_prime.dtype).reshape(t_prime.shape),
+                None, None, None, None)
+
+
+def softmax_contrastive_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
+                             t_prime: torch.Tensor,
+                             diag_offset: Optional[int] = 0,
+                             col_chunk: Optional[int] = None,
+                             impl: str = "auto", group=None) -> torch.Tensor:
+    """Sum-form softmax contrastive loss of the ``(b, n)`` block: the
+    cross-entropy of every row that has a positive plus that of every column
+    that has one (see the module docstring).  Differentiable in ``zimg``,
+    ``ztxt`` and ``t_prime``.
+
+    Args:
+        zimg: ``(b, d)`` image embeddings (L2-normalized by the caller).
+        ztxt: ``(n, d)`` text embeddings.
+        t_prime: scalar; the temperature is ``exp(t_prime)``.
+        diag_offset: column of row 0's positive; ``None``: no positives.
+        col_chunk: columns per kernel pass (forward LSE and backward g
+            band), bounding the workspace to ``O(b · col_chunk)``; ``None``:
+            the whole block, banded in backward only when the bf16 g slab
+            would reach 2³² bytes.
+        impl: ``auto`` (``hip`` on GPU, ``torch`` elsewhere) | ``hip`` (bf16,
+            ``d % 8 == 0``; raises without the built extension) | ``torch``.
+        group: a process group of ``W > 1`` ranks for the one-grid
+            distributed form (``n == W·b``, ``diag_offset == rank·b``);
+            ``None``: this block alone.
+
+    Returns a 0-d tensor; the caller normalises.
+    """
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise ValueError(
+            f"shape mismatch: zimg {tuple(zimg.shape)} ztxt {tuple(ztxt.shape)}")
+    if impl == "auto":
+        impl = "hip" if zimg.is_cuda else "torch"
+    if impl not in ("hip", "torch"):
+        raise ValueError(f"unknown impl {impl!r}")
+    if not _is_distributed(group):
+        group = None
+    else:
+        world, rank = dist.get_world_size(group), dist.get_rank(group)
+        b = zimg.shape[0]
+        if ztxt.shape[0] != world * b or diag_offset != rank * b:
+            raise ValueError(
+                f"the distributed form needs n == W·b and diag_offset == "
+                f"rank·b (got b={b}, n={ztxt.shape[0]}, W={world}, "
+                f"rank={rank}, diag_offset={diag_offset})")
+    return _SoftmaxLoss.apply(zimg, ztxt, t_prime, diag_offset, col_chunk,
+                              impl, group)
+
+
+class DistributedSoftmaxLoss(nn.Module):
+    """All-rank softmax (CLIP) contrastive loss with a module-owned,
+    learnable ``t_prime`` (init ``log(1 / init_temperature)``; the forward
+    clamps it at ``log(max_logit_scale)``, as CLIP does).
+
+    ``forward`` takes the *local* image and text shards ``(b, d)``,
+    all-gathers the text shard (``all_gather_with_grad``: reduce-scatter in
+    backward), evaluates the ``(b, W·b)`` grid with ``diag_offset = rank·b``
+    and returns ``total / (2·gpu_batch_size)``.  At ``W = 1`` that is the
+    symmetric CLIP loss ``(CE(z) + CE(zᵀ)) / 2``; under DDP gradient
+    averaging ``W`` ranks reproduce the single-rank gradients of the global
+    batch.
+    """
+
+    def __init__(self, gpu_batch_size: int, col_chunk: Optional[int] = None,
+                 impl: str = "auto", init_temperature: float = 0.07,
+                 max_logit_scale: float = 100.0):
+        super().__init__()
+        self.t_prime = nn.Parameter(
+            torch.tensor(math.log(1.0 / init_temperature)))
+        self.gpu_batch_size = gpu_batch_size
+        self.col_chunk = col_chunk
+        self.impl = impl
+        self.max_logit_scale = max_logit_scale
+
+    def forward(self, image_embeddings: torch.Tensor,
+                text_embeddings: torch.Tensor, group=None) -> torch.Tensor:
+        world, rank = 1, 0
+        if dist.is_available() and dist.is_initialized():
+            world, rank = dist.get_world_size(group), dist.get_rank(group)
+        t_prime = self.t_prime.clamp(max=math.log(self.max_logit_scale))
+        all_txt = all_gather_with_grad(text_embeddings, group=group)
+        if world > 1 and group is None:
+            group = dist.group.WORLD
+        total = softmax_contrastive_loss(
+            image_embeddings, all_txt, t_prime,
+            diag_offset=rank * text_embeddings.shape[0],
+            col_chunk=self.col_chunk, impl=self.impl,
+            group=group if world > 1 else None)
+        return total / (2 * self.gpu_batch_size)

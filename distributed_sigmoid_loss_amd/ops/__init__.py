@@ -27,6 +27,10 @@ exposes:
   counts of the scores above a threshold, a second (integer) reduction over
   the same never-materialized pair grid (``losses/retrieval.py`` turns them
   into ranks and recall@k).
+- softmax (InfoNCE) loss: :func:`pair_lse` — row and column log-sum-exp of
+  the pair grid — and :func:`softmax_g` — its dL/dlogit slab and per-tile
+  ``Σ g·s`` partials (``losses/softmax_loss.py`` builds the loss, its
+  backward and the distributed form on them).
 
 Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
@@ -186,6 +190,23 @@ def _load():
     lib.pair_rank_counts_bf16.restype = ctypes.c_int
     lib.pair_rank_counts_bf16.argtypes = (
         [ctypes.c_void_p] * 7 + [ctypes.c_int] * 4)
+    if not hasattr(lib, "softmax_lse_bf16"):
+        _lib_err = (f"stale HIP extension at {SO_PATH} (no softmax kernels); "
+                    "rebuild with: "
+                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
+        return None
+    lib.softmax_tile_dim.restype = ctypes.c_int
+    lib.softmax_tile_dim.argtypes = []
+    # (stream, zimg, ztxt, t', row_ws, col_ws, row_lse, col_lse, b, n, d)
+    lib.softmax_lse_bf16.restype = ctypes.c_int
+    lib.softmax_lse_bf16.argtypes = (
+        [ctypes.c_void_p] * 8 + [ctypes.c_int] * 3)
+    # (stream, zimg, ztxt, t', row_lse, row_w, col_lse, col_w, g, gs_ws,
+    #  b, n, d, ldg, diag)
+    lib.softmax_g_bf16.restype = ctypes.c_int
+    lib.softmax_g_bf16.argtypes = (
+        [ctypes.c_void_p] * 10 + [ctypes.c_int] * 3 + [ctypes.c_longlong]
+        + [ctypes.c_int])
     _lib = lib
     return _lib
 
@@ -944,6 +965,126 @@ def pair_rank_counts(zimg: torch.Tensor, ztxt: torch.Tensor,
         _ptr(col_thr), _ptr(row_cnt), _ptr(col_cnt), b, n, d, diag),
         "pair_rank_counts_bf16")
     return row_cnt, col_cnt
+
+
+def _softmax_block(what: str, zimg: torch.Tensor, ztxt: torch.Tensor,
+                   t_prime: torch.Tensor):
+    """Validate the embeddings of a softmax op; returns the contiguous
+    detached pair, ``t'`` as a device fp32 scalar and the tile counts."""
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings, got "
+            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
+    _validate(zimg, ztxt, "bf16")
+    if ztxt.device != zimg.device:
+        raise RuntimeError("zimg and ztxt must be on the same device")
+    b, n = zimg.shape[0], ztxt.shape[0]
+    if b < 1 or n < 1:
+        raise RuntimeError(f"{what} needs a non-empty block")
+    tile = _require_lib().softmax_tile_dim()
+    return (zimg.detach().contiguous(), ztxt.detach().contiguous(),
+            _prep_scalar(t_prime, zimg.device), -(-b // tile), -(-n // tile))
+
+
+def _softmax_side(name: str, lse, w, length: int, device):
+    """Validate one side (rows or columns) of :func:`softmax_g`: both vectors
+    or neither."""
+    if (lse is None) != (w is None):
+        raise RuntimeError(f"{name}_lse and {name}_w must be given together")
+    for what, v in ((f"{name}_lse", lse), (f"{name}_w", w)):
+        if v is not None and (
+                v.device != device or v.dtype != torch.float32
+                or v.shape != (length,) or not v.is_contiguous()):
+            raise RuntimeError(
+                f"{what} must be a contiguous fp32 ({length},) tensor on "
+                f"{device} (got {v.dtype} {tuple(v.shape)} on {v.device})")
+    return lse, w
+
+
+def pair_lse(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
+             rows: bool = True, cols: bool = True):
+    """Log-sum-exp of every row and every column of the ``(b, n)`` logit grid
+    ``z = exp(t')·zimg @ ztxtᵀ`` without materializing it →
+    ``(row_lse (b,) | None, col_lse (n,) | None)``, fresh fp32 tensors; a side
+    that is switched off is skipped and returned as ``None``.
+
+    One MFMA pass leaves per-tile ``(max, Σ exp(z − max))`` partials in
+    workspaces from the torch allocator (``O((b + n) · tiles)`` floats), a
+    second kernel folds them in tile order: no float atomics, bitwise
+    reproducible.  ``t_prime`` is read on the device (no host sync).  Column
+    chunks (``ztxt[j0:j1]``) and ranks compose in the caller:
+    ``torch.logaddexp`` of the row results, ``torch.logsumexp`` over ranks'
+    column results.  No autograd."""
+    zi, zt, tp, tiles_m, tiles_n = _softmax_block("pair_lse", zimg, ztxt,
+                                                  t_prime)
+    if not rows and not cols:
+        return None, None
+    lib = _require_lib()
+    b, d = zi.shape
+    n = zt.shape[0]
+    dev = zi.device
+
+    def side(on, tiles, length):
+        if not on:
+            return None, None
+        return (torch.empty((tiles, length, 2), device=dev,
+                            dtype=torch.float32),
+                torch.empty(length, device=dev, dtype=torch.float32))
+
+    row_ws, row_lse = side(rows, tiles_n, b)
+    col_ws, col_lse = side(cols, tiles_m, n)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.softmax_lse_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(row_ws),
+        _ptr(col_ws), _ptr(row_lse), _ptr(col_lse), b, n, d),
+        "softmax_lse_bf16")
+    return row_lse, col_lse
+
+
+def softmax_g(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
+              row_lse: Optional[torch.Tensor], row_w: Optional[torch.Tensor],
+              col_lse: Optional[torch.Tensor], col_w: Optional[torch.Tensor],
+              diag_offset: Optional[int], g: Optional[torch.Tensor] = None):
+    """dL/dlogit of the softmax contrastive loss over the ``(b, n)`` block →
+    ``(g, gs_partials)``:
+
+    ``g_ij = row_w_i·exp(z_ij − row_lse_i) + col_w_j·exp(z_ij − col_lse_j)
+    − [j == i + diag_offset]·(row_w_i + col_w_j)``, bf16, and one fp32
+    ``Σ g_ij·s_ij`` (``s = z / t``) per 128×128 tile, each reduced in a fixed
+    order (``dt' = t·gs_partials.sum()``).
+
+    The LSE and weight vectors are fp32 ``(b,)`` / ``(n,)``; a side given as
+    ``None, None`` adds no term.  ``diag_offset=None``: no positives.  ``g``
+    may be the caller's ``(b, n)`` view with unit column stride — a column
+    band of a wider slab: the view carries the offset and its row stride,
+    so slicing, not pointer arithmetic, bounds the write; only its elements
+    are touched.  No autograd."""
+    zi, zt, tp, tiles_m, tiles_n = _softmax_block("softmax_g", zimg, ztxt,
+                                                  t_prime)
+    lib = _require_lib()
+    b, d = zi.shape
+    n = zt.shape[0]
+    dev = zi.device
+    row_lse, row_w = _softmax_side("row", row_lse, row_w, b, dev)
+    col_lse, col_w = _softmax_side("col", col_lse, col_w, n, dev)
+    if g is None:
+        g = torch.empty((b, n), device=dev, dtype=torch.bfloat16)
+    elif (g.device != dev or g.dtype != torch.bfloat16 or g.shape != (b, n)
+          or g.stride(1) != 1 or (b > 1 and g.stride(0) < n)):
+        raise RuntimeError(
+            f"g must be a bf16 ({b}, {n}) view with unit column stride on "
+            f"{dev} (got {g.dtype} {tuple(g.shape)}, strides "
+            f"{tuple(g.stride())} on {g.device})")
+    gs = torch.empty(tiles_m * tiles_n, device=dev, dtype=torch.float32)
+    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
+    if not -(2 ** 31) < diag < 2 ** 31:
+        diag = _DIAG_NONE       # no positive can lie inside an int32 block
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.softmax_g_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(row_lse),
+        _ptr(row_w), _ptr(col_lse), _ptr(col_w), _ptr(g), _ptr(gs), b, n, d,
+        ctypes.c_longlong(max(g.stride(0), n)), diag), "softmax_g_bf16")
+    return g, gs
 
 
 class _FusedL2Normalize(torch.autograd.Function):

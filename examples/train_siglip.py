@@ -15,6 +15,9 @@ Single GPU:
 CPU smoke (gloo):
     python examples/train_siglip.py --device cpu --batch-per-gpu 8 --dim 64
 
+``--loss softmax`` trains against the softmax (CLIP / InfoNCE) baseline loss
+instead of the sigmoid one.
+
 ``--eval-every N`` prints the retrieval metrics of the current batch every N
 steps (image→text and text→image recall@1/5 and the median rank, over the
 global batch): the loss alone barely moves with retrieval quality at the
@@ -35,6 +38,7 @@ import torch.distributed as dist
 
 from distributed_sigmoid_loss_amd import (
     DistributedSigmoidLoss,
+    DistributedSoftmaxLoss,
     distributed_retrieval_ranks,
     recall_at_k,
 )
@@ -65,6 +69,10 @@ def main():
     p.add_argument("--strategy", choices=["ring", "all_gather"],
                    default="ring")
     p.add_argument("--quant", choices=["bf16", "fp8", "mixed"], default="bf16")
+    p.add_argument("--loss", choices=["sigmoid", "softmax"],
+                   default="sigmoid",
+                   help="softmax: the CLIP / InfoNCE baseline (bf16 only; "
+                        "--strategy and --quant do not apply)")
     p.add_argument("--device", default=None)
     p.add_argument("--log-every", type=int, default=10)
     p.add_argument("--eval-every", type=int, default=0,
@@ -78,9 +86,12 @@ def main():
     set_seed(1234)  # identical tower init on every rank
 
     model = TwoTowerModel(args.dim, args.dim).to(device=device, dtype=dtype)
-    loss_mod = DistributedSigmoidLoss(
-        args.batch_per_gpu, strategy=args.strategy,
-        quant=args.quant if device == "cuda" else "bf16").to(device)
+    if args.loss == "softmax":
+        loss_mod = DistributedSoftmaxLoss(args.batch_per_gpu).to(device)
+    else:
+        loss_mod = DistributedSigmoidLoss(
+            args.batch_per_gpu, strategy=args.strategy,
+            quant=args.quant if device == "cuda" else "bf16").to(device)
     # Loss params (t_prime, bias) must reach the optimizer too
     # (reference README.md:20).
     opt = torch.optim.AdamW(
@@ -111,7 +122,9 @@ def main():
                                for k, v in timer.summary().items())
             print(f"step {step + 1:4d}  loss={float(loss.detach()):.4f}  "
                   f"t={float(loss_mod.t_prime.detach().exp()):.3f}  "
-                  f"bias={float(loss_mod.bias.detach()):.3f}  {phases}", flush=True)
+                  + (f"bias={float(loss_mod.bias.detach()):.3f}  "
+                     if hasattr(loss_mod, "bias") else "")
+                  + phases, flush=True)
             timer.rows.clear()
 
         if args.eval_every > 0 and (step + 1) % args.eval_every == 0:

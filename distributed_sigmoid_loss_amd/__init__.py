@@ -18,6 +18,11 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
 - ``retrieval_ranks`` / ``recall_at_k`` / ``distributed_retrieval_ranks`` —
   the retrieval rank of every matching pair in both directions, counted by a
   fused HIP kernel over the same never-materialized grid.
+- ``pair_topk`` / ``retrieval_topk`` / ``distributed_retrieval_topk`` /
+  ``merge_topk`` — the ``k`` best scoring partners of every sample in both
+  directions, with the positive left out on request (hard-negative mining),
+  from a fused HIP kernel that keeps running per-row lists across column
+  tiles; exact tie rule, bitwise reproducible, mergeable over column chunks.
 - ``DistributedSoftmaxLoss`` / ``softmax_contrastive_loss`` — the softmax
   (CLIP / InfoNCE) baseline with the same contract: fused row and column
   log-sum-exp forward, fused dL/dlogit backward, single device or one grid
@@ -38,6 +43,11 @@ from .losses.retrieval import (
     retrieval_ranks,
     recall_at_k,
     distributed_retrieval_ranks,
+    TopK,
+    pair_topk,
+    merge_topk,
+    retrieval_topk,
+    distributed_retrieval_topk,
 )
 from .losses.softmax_loss import (
     DistributedSoftmaxLoss,
@@ -61,6 +71,11 @@ __all__ = [
     "retrieval_ranks",
     "recall_at_k",
     "distributed_retrieval_ranks",
+    "TopK",
+    "pair_topk",
+    "merge_topk",
+    "retrieval_topk",
+    "distributed_retrieval_topk",
     "DistributedSoftmaxLoss",
     "softmax_contrastive_loss",
     "neighbour_exchange",

@@ -19,6 +19,17 @@ one MFMA pass over the grid, the ``(b, n)`` logits never reach memory.  Counts
 are integers and add over column chunks and over ranks, so the same kernel
 serves the single-device and the all-gathered distributed case, and results
 are bitwise reproducible.
+
+Retrieval itself — which partners score highest, and how high — is
+:func:`pair_topk`: for every row the ``k`` best candidates ``j ≠ i +
+diag_offset`` in the total order "higher score first, among equal scores the
+lower column first", ``(−inf, −1)`` once the candidates run out.  With the
+positive excluded these are the row's hardest negatives.  The order is total,
+so results are bitwise reproducible and :func:`merge_topk` of results over
+disjoint column chunks equals the single call.  On GPU the lists come from
+the fused HIP kernel (``ops.pair_topk``) in one pass over the grid;
+:func:`retrieval_topk` runs both directions, :func:`distributed_retrieval_topk`
+the global batch.
 """
 
 from __future__ import annotations
@@ -220,3 +231,167 @@ def distributed_retrieval_ranks(zimg: torch.Tensor, ztxt: torch.Tensor,
             dist.reduce_scatter_tensor(local, col_cnt, op=dist.ReduceOp.SUM,
                                        group=group)
     return RetrievalRanks(row_cnt.long(), local.long())
+
+
+class TopK(NamedTuple):
+    """``scores`` ``(rows, k)`` (fp32; fp64 for fp64 inputs), best first, and
+    int64 ``indices`` ``(rows, k)``; ``(−inf, −1)`` in the slots past the
+    last candidate."""
+    scores: torch.Tensor
+    indices: torch.Tensor
+
+
+def _torch_pair_topk(zimg, ztxt, k, diag_offset, row_chunk=_TORCH_ROW_CHUNK):
+    """Row-chunked torch composite with the contract of the kernel, the tie
+    rule included (a stable descending sort keeps the lower column first)."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    dev = zimg.device
+    cdt = _compute_dtype(zimg)
+    scores = torch.full((b, k), -math.inf, device=dev, dtype=cdt)
+    cols = torch.full((b, k), -1, device=dev, dtype=torch.long)
+    kk = min(k, n)
+    zt = ztxt.detach().to(cdt)
+    col_ids = torch.arange(n, device=dev)
+    for r0 in range(0, b, max(1, int(row_chunk))):
+        r1 = min(b, r0 + max(1, int(row_chunk)))
+        s = zimg[r0:r1].detach().to(cdt) @ zt.T
+        pos = None
+        if diag_offset is not None:
+            pos = torch.arange(r0, r1, device=dev) + int(diag_offset)
+            s.masked_fill_(col_ids[None, :] == pos[:, None], -math.inf)
+        top_s, top_c = torch.sort(s, dim=1, descending=True, stable=True)
+        top_s, top_c = top_s[:, :kk].clone(), top_c[:, :kk].clone()
+        if pos is not None:
+            # The excluded column sorts behind every candidate; it shows up
+            # only where the candidates ran out.
+            gone = top_c == pos[:, None]
+            top_s[gone] = -math.inf
+            top_c[gone] = -1
+        scores[r0:r1, :kk] = top_s
+        cols[r0:r1, :kk] = top_c
+    return scores, cols
+
+
+def pair_topk(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
+              diag_offset: Optional[int] = None, col_base: int = 0,
+              impl: str = "auto") -> TopK:
+    """The ``k`` best scoring columns of every row of the score grid.
+
+    The candidates of row ``i`` are the columns ``j`` of ``ztxt`` with ``j ≠
+    i + diag_offset`` (``None``: all columns), ordered by higher score first
+    and, among equal scores, lower column first (``+0`` equals ``−0``); slot
+    ``q`` holds the ``q``-th candidate and ``(−inf, −1)`` past the last one.
+    Indices are ``column + col_base``.  No autograd.
+
+    ``impl``: ``auto`` (``hip`` on GPU for bf16 inputs and ``k`` within the
+    kernel's range, ``torch`` otherwise) | ``hip`` (bf16, ``d % 8 == 0``,
+    ``k ≤ ops.pair_topk_max_k()``; raises otherwise) | ``torch`` (row-chunked
+    composite, any ``k``).
+    """
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings, got "
+            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    if impl == "auto":
+        impl = "torch"
+        if (zimg.is_cuda and zimg.dtype == torch.bfloat16
+                and ztxt.dtype == torch.bfloat16):
+            from .. import ops
+            if k <= ops.pair_topk_max_k():
+                impl = "hip"
+    if impl == "hip":
+        from .. import ops
+        scores, cols = ops.pair_topk(zimg, ztxt, k, diag_offset)
+        cols = cols.long()
+    elif impl == "torch":
+        if zimg.shape[0] < 1 or ztxt.shape[0] < 1:
+            raise RuntimeError("pair_topk needs a non-empty block")
+        scores, cols = _torch_pair_topk(zimg, ztxt, k, diag_offset)
+    else:
+        raise ValueError(f"unknown impl {impl!r}")
+    if col_base:
+        cols = torch.where(cols >= 0, cols + int(col_base), cols)
+    return TopK(scores, cols)
+
+
+def merge_topk(parts: Sequence[TopK], k: Optional[int] = None) -> TopK:
+    """Merge results over disjoint column sets (same rows, global indices)
+    under the same total order; ``−1`` slots are ignored.  ``k`` defaults to
+    the first part's.  A chunked call is ``pair_topk(zimg, ztxt[j0:j1], k,
+    diag_offset − j0, col_base=j0)`` per chunk and one merge, and equals the
+    single call bit for bit."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_topk needs at least one part")
+    k = parts[0].scores.shape[1] if k is None else int(k)
+    if k < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    scores = torch.cat([p.scores for p in parts], dim=1)
+    idx = torch.cat([p.indices for p in parts], dim=1)
+    last = torch.iinfo(torch.long).max
+    fill = idx < 0
+    key = torch.where(fill, torch.full_like(idx, last), idx)
+    sc = scores.masked_fill(fill, -math.inf)
+    # Lexicographic (score descending, index ascending): order by the minor
+    # key first, then stably by the major one.
+    key, o = torch.sort(key, dim=1, stable=True)
+    sc = sc.gather(1, o)
+    sc, o = torch.sort(sc, dim=1, descending=True, stable=True)
+    key = key.gather(1, o)
+    out_s = torch.full((sc.shape[0], k), -math.inf, device=sc.device,
+                       dtype=sc.dtype)
+    out_i = torch.full((sc.shape[0], k), -1, device=sc.device,
+                       dtype=torch.long)
+    kk = min(k, sc.shape[1])
+    out_s[:, :kk] = sc[:, :kk]
+    out_i[:, :kk] = torch.where(key[:, :kk] == last,
+                                torch.full_like(key[:, :kk], -1),
+                                key[:, :kk])
+    return TopK(out_s, out_i)
+
+
+def retrieval_topk(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
+                   diag_offset: Optional[int] = None, impl: str = "auto"):
+    """``(i2t, t2i)``: for every image its ``k`` best texts and for every
+    text its ``k`` best images (:class:`TopK` each).  With an integer
+    ``diag_offset`` the pair ``(i, i + diag_offset)`` is left out on both
+    sides — the lists are the hardest negatives; ``None`` is plain
+    retrieval.  The text side is the same op with the operands exchanged."""
+    i2t = pair_topk(zimg, ztxt, k, diag_offset, impl=impl)
+    t2i = pair_topk(ztxt, zimg, k,
+                    None if diag_offset is None else -int(diag_offset),
+                    impl=impl)
+    return i2t, t2i
+
+
+def distributed_retrieval_topk(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
+                               exclude_positive: bool = False, group=None,
+                               impl: str = "auto"):
+    """``(i2t, t2i)`` of this rank's ``b`` images against all ``W·b`` texts
+    and of its ``b`` texts against all ``W·b`` images, with global indices
+    (equal ``b`` on every rank; the positive of local image ``i`` is local
+    text ``i``, left out when ``exclude_positive``).
+
+    The text shard is all-gathered for the image side and the image shard for
+    the text side; each side is one :func:`pair_topk` pass over a ``(b,
+    W·b)`` block and complete on its own, so nothing is reduced.  World size
+    1 is :func:`retrieval_topk`."""
+    if (not dist.is_available() or not dist.is_initialized()
+            or dist.get_world_size(group) == 1):
+        return retrieval_topk(zimg, ztxt, k, 0 if exclude_positive else None,
+                              impl=impl)
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    b = zimg.shape[0]
+    if ztxt.shape[0] != b:
+        raise RuntimeError("distributed_retrieval_topk needs paired shards")
+    off = rank * b if exclude_positive else None
+    with torch.no_grad():
+        zt_all = all_gather_with_grad(ztxt.detach(), group)
+        i2t = pair_topk(zimg.detach(), zt_all, k, off, impl=impl)
+        del zt_all
+        zi_all = all_gather_with_grad(zimg.detach(), group)
+        t2i = pair_topk(ztxt.detach(), zi_all, k, off, impl=impl)
+    return i2t, t2i

@@ -31,6 +31,11 @@ exposes:
   the pair grid — and :func:`softmax_g` — its dL/dlogit slab and per-tile
   ``Σ g·s`` partials (``losses/softmax_loss.py`` builds the loss, its
   backward and the distributed form on them).
+- retrieval itself: :func:`pair_topk` — the ``k`` best scoring columns of
+  every row of the pair grid, optionally without the positive (hard-negative
+  mining), from running per-row lists kept across column tiles
+  (``losses/retrieval.py`` adds both directions, chunk merging and the
+  distributed form).
 
 Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
@@ -207,6 +212,21 @@ def _load():
     lib.softmax_g_bf16.argtypes = (
         [ctypes.c_void_p] * 10 + [ctypes.c_int] * 3 + [ctypes.c_longlong]
         + [ctypes.c_int])
+    if not hasattr(lib, "pair_topk_bf16"):
+        _lib_err = (f"stale HIP extension at {SO_PATH} (no top-k kernels); "
+                    "rebuild with: "
+                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
+        return None
+    for fn in (lib.pair_topk_max_k, lib.pair_topk_tile_dim):
+        fn.restype = ctypes.c_int
+        fn.argtypes = []
+    lib.pair_topk_capacity.restype = ctypes.c_int
+    lib.pair_topk_capacity.argtypes = [ctypes.c_int]
+    # (stream, zimg, ztxt, ws_s, ws_c, out_s, out_c, b, n, d, diag, k,
+    #  n_splits)
+    lib.pair_topk_bf16.restype = ctypes.c_int
+    lib.pair_topk_bf16.argtypes = (
+        [ctypes.c_void_p] * 7 + [ctypes.c_int] * 6)
     _lib = lib
     return _lib
 
@@ -965,6 +985,71 @@ def pair_rank_counts(zimg: torch.Tensor, ztxt: torch.Tensor,
         _ptr(col_thr), _ptr(row_cnt), _ptr(col_cnt), b, n, d, diag),
         "pair_rank_counts_bf16")
     return row_cnt, col_cnt
+
+
+def pair_topk_max_k() -> int:
+    """Largest ``k`` :func:`pair_topk` serves."""
+    return _require_lib().pair_topk_max_k()
+
+
+def pair_topk(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
+              diag_offset: Optional[int] = None,
+              n_splits: Optional[int] = None):
+    """The ``k`` best scoring columns of every row of the ``(b, n)`` score
+    grid ``s = zimg @ ztxtᵀ`` without materializing it →
+    ``(scores (b, k) fp32, columns (b, k) int32)``.
+
+    The candidates of row ``i`` are the columns ``j ≠ i + diag_offset``
+    (``diag_offset=None``: all of them), ordered by higher score first and,
+    among equal scores, lower column first; slots past the last candidate
+    hold ``(−inf, −1)``.  ``1 ≤ k ≤ pair_topk_max_k()``.
+
+    A workgroup keeps running lists for 128 rows over one of ``n_splits``
+    contiguous spans of column tiles and a second kernel merges the spans'
+    lists (workspace from the torch allocator: ``n_splits · b · capacity``
+    pairs).  ``n_splits`` defaults to the smallest value that gives two
+    workgroups per CU and is clamped to ``[1, ceil(n / tile)]``; the order
+    is total, so the result does not depend on it and is bitwise
+    reproducible.  No atomics, no autograd."""
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings, got "
+            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
+    _validate(zimg, ztxt, "bf16")
+    if ztxt.device != zimg.device:
+        raise RuntimeError("zimg and ztxt must be on the same device")
+    b, d = zimg.shape
+    n = ztxt.shape[0]
+    if b < 1 or n < 1:
+        raise RuntimeError("pair_topk needs a non-empty block")
+    lib = _require_lib()
+    k = int(k)
+    if not 1 <= k <= lib.pair_topk_max_k():
+        raise RuntimeError(
+            f"pair_topk serves 1 <= k <= {lib.pair_topk_max_k()} (got {k}); "
+            "pass impl='torch' for more")
+    zi, zt = zimg.detach().contiguous(), ztxt.detach().contiguous()
+    dev = zi.device
+    tile = lib.pair_topk_tile_dim()
+    tiles_m, tiles_n = -(-b // tile), -(-n // tile)
+    if n_splits is None:
+        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+        n_splits = -(-2 * n_cu // tiles_m)
+    n_splits = max(1, min(int(n_splits), tiles_n))
+    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
+    if not -(2 ** 31) < diag < 2 ** 31:
+        diag = _DIAG_NONE       # no positive can lie inside an int32 block
+    cap = lib.pair_topk_capacity(k)
+    ws_s = torch.empty((n_splits, b, cap), device=dev, dtype=torch.float32)
+    ws_c = torch.empty((n_splits, b, cap), device=dev, dtype=torch.int32)
+    out_s = torch.empty((b, k), device=dev, dtype=torch.float32)
+    out_c = torch.empty((b, k), device=dev, dtype=torch.int32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.pair_topk_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(ws_s), _ptr(ws_c),
+        _ptr(out_s), _ptr(out_c), b, n, d, diag, k, n_splits),
+        "pair_topk_bf16")
+    return out_s, out_c
 
 
 def _softmax_block(what: str, zimg: torch.Tensor, ztxt: torch.Tensor,

@@ -22,6 +22,10 @@ instead of the sigmoid one.
 steps (image→text and text→image recall@1/5 and the median rank, over the
 global batch): the loss alone barely moves with retrieval quality at the
 SigLIP initialisation.
+
+``--hard-negatives K`` (with ``--eval-every``) adds one line per eval: the
+mean margin between the positive score and the mean of the K hardest negative
+scores, image→text and text→image, over the global batch.
 """
 
 from __future__ import annotations
@@ -40,6 +44,8 @@ from distributed_sigmoid_loss_amd import (
     DistributedSigmoidLoss,
     DistributedSoftmaxLoss,
     distributed_retrieval_ranks,
+    distributed_retrieval_topk,
+    positive_scores,
     recall_at_k,
 )
 from distributed_sigmoid_loss_amd.models import TwoTowerModel
@@ -78,6 +84,9 @@ def main():
     p.add_argument("--eval-every", type=int, default=0,
                    help="print retrieval recall of the current batch every N "
                         "steps (0 = off)")
+    p.add_argument("--hard-negatives", type=int, default=0,
+                   help="with --eval-every: also print the mean margin of "
+                        "the positive over the K hardest negatives (0 = off)")
     args = p.parse_args()
 
     rank, local_rank, world = init_from_env()
@@ -139,6 +148,23 @@ def main():
                       f"median={int(ranks.i2t.median())}  "
                       f"t2i R@1={r_t2i['R@1']:.4f} R@5={r_t2i['R@5']:.4f} "
                       f"median={int(ranks.t2i.median())}", flush=True)
+            if args.hard_negatives > 0:
+                # Collective as well.  Every rank's margins cover its shard
+                # against the global batch; their mean is averaged over ranks.
+                neg_i2t, neg_t2i = distributed_retrieval_topk(
+                    zi.detach(), zt.detach(), args.hard_negatives,
+                    exclude_positive=True)
+                pos = positive_scores(zi.detach(), zt.detach(), 0).float()
+                margins = torch.stack([
+                    (pos - neg.scores.float().mean(1)).mean()
+                    for neg in (neg_i2t, neg_t2i)])
+                if world > 1:
+                    dist.all_reduce(margins)
+                    margins /= world
+                if rank == 0:
+                    print(f"hardneg {step + 1:4d}  k={args.hard_negatives}  "
+                          f"i2t margin={float(margins[0]):.4f}  "
+                          f"t2i margin={float(margins[1]):.4f}", flush=True)
 
     if device == "cuda":
         torch.cuda.synchronize()

@@ -27,6 +27,11 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
   (CLIP / InfoNCE) baseline with the same contract: fused row and column
   log-sum-exp forward, fused dL/dlogit backward, single device or one grid
   across ranks.
+- ``sigmoid_contrastive_loss_ids`` — the sigmoid loss with sample-ID labels:
+  int64 ids decide what is a positive, a negative or an ignored pair (several
+  captions per image, repeated samples, padding rows), from a fused HIP kernel
+  with a saved-g and a band-recompute backward; ``DistributedSigmoidLoss``
+  takes ``image_ids`` / ``text_ids``.
 
 The compute path is PyTorch-ROCm + HIP/CDNA4 kernels + RCCL over xGMI; there
 are no CUDA compatibility layers and no multi-backend dispatch.
@@ -53,6 +58,7 @@ from .losses.softmax_loss import (
     DistributedSoftmaxLoss,
     softmax_contrastive_loss,
 )
+from .losses.id_labels import sigmoid_contrastive_loss_ids
 from .parallel.ring import (
     neighbour_exchange,
     neighbour_exchange_bidir,
@@ -78,6 +84,7 @@ __all__ = [
     "distributed_retrieval_topk",
     "DistributedSoftmaxLoss",
     "softmax_contrastive_loss",
+    "sigmoid_contrastive_loss_ids",
     "neighbour_exchange",
     "neighbour_exchange_bidir",
     "neighbour_exchange_with_grad",

@@ -37,6 +37,7 @@ from .functional import (
     chunk_loss_fwd,
     chunk_loss_bwd,
 )
+from .id_labels import sigmoid_contrastive_loss_ids
 from ..parallel.collectives import all_gather_with_grad, _backend_is_gloo
 from ..parallel.ring import (
     neighbour_exchange_with_grad,
@@ -363,6 +364,18 @@ class DistributedSigmoidLoss(nn.Module):
         - ``"ring"`` — pipelined P2P ring (xGMI point-to-point) with
           comm/compute overlap and reduce-scatter backward.
 
+    Sample-ID labels: ``forward(..., image_ids=, text_ids=)`` (both or
+    neither; int64 ``(b,)`` each) replaces the positional labels by
+    ``sigmoid_contrastive_loss_ids`` — ids equal: positive
+    (``duplicates="positive"``), or the position stays the only positive and
+    other pairs with equal ids are ignored (``"ignore"``); a negative id
+    masks its row / column.  The text ids are all-gathered next to the text
+    shard and the ``(b, W·b)`` grid is one call with ``diag_offset =
+    rank·b``.  Supported with ``strategy="all_gather"`` (or any strategy at
+    ``W = 1``) and ``quant="bf16"``; anything else raises.  The result is
+    still divided by ``gpu_batch_size`` — not by the number of unmasked rows
+    — so a batch with masked rows weighs less, it is not renormalised.
+
     Works with DistributedDataParallel (DDP) only (not DataParallel); pass
     ``t_prime``/``bias`` to your optimizer like any other parameter
     (reference ``README.md:19-20``).
@@ -393,8 +406,40 @@ class DistributedSigmoidLoss(nn.Module):
             from .. import ops as _ops
             _ops.load_tuned_gemms()
 
+    def _forward_ids(self, image_embeddings, text_embeddings, group,
+                     image_ids, text_ids, duplicates):
+        world, rank = _world_and_rank(group)
+        if self.quant != "bf16" or (self.strategy == "ring" and world > 1):
+            raise ValueError(
+                "sample-ID labels are supported with strategy='all_gather' "
+                "(or a single rank) and quant='bf16' (got strategy="
+                f"{self.strategy!r}, quant={self.quant!r}, world={world})")
+        b_txt = text_embeddings.shape[0]
+        text_ids = text_ids.to(device=text_embeddings.device,
+                               dtype=torch.int64).contiguous()
+        all_txt = all_gather_with_grad(text_embeddings, group=group)
+        all_ids = text_ids
+        if world > 1:
+            all_ids = torch.empty(world * b_txt, device=text_ids.device,
+                                  dtype=torch.int64)
+            dist.all_gather_into_tensor(all_ids, text_ids, group=group)
+        total = sigmoid_contrastive_loss_ids(
+            image_embeddings, all_txt, self.t_prime, self.bias, image_ids,
+            all_ids, duplicates=duplicates, diag_offset=rank * b_txt,
+            col_chunk=self.col_chunk, impl=self.impl)
+        return total / self.gpu_batch_size
+
     def forward(self, image_embeddings: torch.Tensor,
-                text_embeddings: torch.Tensor, group=None) -> torch.Tensor:
+                text_embeddings: torch.Tensor, group=None,
+                image_ids: Optional[torch.Tensor] = None,
+                text_ids: Optional[torch.Tensor] = None,
+                duplicates: str = "positive") -> torch.Tensor:
+        if (image_ids is None) != (text_ids is None):
+            raise ValueError(
+                "image_ids and text_ids must be given together")
+        if image_ids is not None:
+            return self._forward_ids(image_embeddings, text_embeddings,
+                                     group, image_ids, text_ids, duplicates)
         world, rank = _world_and_rank(group)
         b_txt = text_embeddings.shape[0]
         if self.strategy == "all_gather" or world == 1:

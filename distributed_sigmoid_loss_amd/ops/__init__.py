@@ -36,6 +36,11 @@ exposes:
   mining), from running per-row lists kept across column tiles
   (``losses/retrieval.py`` adds both directions, chunk merging and the
   distributed form).
+- sample-ID labels: :func:`sigmoid_ids` — the sigmoid loss whose positives,
+  negatives and ignored pairs come from int64 id vectors (several positives
+  per row, duplicates switched off, padding rows), as per-tile
+  ``(loss, Σ g·s, Σ g)`` partials plus the optional dL/dlogit slab
+  (``losses/id_labels.py`` builds the loss and its two backward regimes).
 
 Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
@@ -227,6 +232,19 @@ def _load():
     lib.pair_topk_bf16.restype = ctypes.c_int
     lib.pair_topk_bf16.argtypes = (
         [ctypes.c_void_p] * 7 + [ctypes.c_int] * 6)
+    if not hasattr(lib, "sigmoid_ids_bf16"):
+        _lib_err = (f"stale HIP extension at {SO_PATH} (no sample-ID "
+                    "kernels); rebuild with: "
+                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
+        return None
+    lib.sigmoid_ids_tile_dim.restype = ctypes.c_int
+    lib.sigmoid_ids_tile_dim.argtypes = []
+    # (stream, zimg, ztxt, t', bias, img_ids, txt_ids, g, ws, b, n, d, ldg,
+    #  diag, mode)
+    lib.sigmoid_ids_bf16.restype = ctypes.c_int
+    lib.sigmoid_ids_bf16.argtypes = (
+        [ctypes.c_void_p] * 9 + [ctypes.c_int] * 3 + [ctypes.c_longlong]
+        + [ctypes.c_int] * 2)
     _lib = lib
     return _lib
 
@@ -1170,6 +1188,88 @@ def softmax_g(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
         _ptr(row_w), _ptr(col_lse), _ptr(col_w), _ptr(g), _ptr(gs), b, n, d,
         ctypes.c_longlong(max(g.stride(0), n)), diag), "softmax_g_bf16")
     return g, gs
+
+
+_DUPLICATES = {"positive": 0, "ignore": 1}
+
+
+def sigmoid_ids(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
+                bias: torch.Tensor, img_ids: torch.Tensor,
+                txt_ids: torch.Tensor, duplicates: str = "positive",
+                diag_offset: Optional[int] = None,
+                g: Optional[torch.Tensor] = None, want_g: bool = True):
+    """Sigmoid contrastive loss with sample-ID labels over the ``(b, n)``
+    block → ``(partials (tiles, 3) fp32, g | None)``.
+
+    With ``z_ij = exp(t')·<zimg_i, ztxt_j> + bias``: a pair with a negative
+    id on either side is masked; ``duplicates="positive"`` makes a pair
+    positive where the ids are equal; ``"ignore"`` makes ``j == i +
+    diag_offset`` the positive (``None``: none) and masks every other pair
+    with equal ids; the rest are negatives.  Per 128×128 tile (row-major tile
+    order) ``partials`` holds ``Σ softplus(−l·z)``, ``Σ g·s`` and ``Σ g``
+    over the pairs that are not masked, with ``g = −l·σ(−l·z)`` and
+    ``s = (z − bias) / t``; each is reduced in a fixed order, so the result
+    is bitwise reproducible and the same with and without ``g``.
+
+    Ids are contiguous int64 ``(b,)`` / ``(n,)`` on the embeddings' device
+    and are compared as 64-bit values.  ``want_g=False`` runs the loss-only
+    kernel and returns ``g`` as ``None``.  Otherwise ``g`` (bf16, 0 where
+    masked) is allocated here or is the caller's ``(b, n)`` view with unit
+    column stride — a column band of a wider slab: the view carries the
+    offset and its row stride, so slicing, not pointer arithmetic, bounds the
+    write; only its elements are touched.  ``t_prime`` and ``bias`` are read
+    on the device (no host sync).  No autograd."""
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings, got "
+            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
+    _validate(zimg, ztxt, "bf16")
+    if ztxt.device != zimg.device:
+        raise RuntimeError("zimg and ztxt must be on the same device")
+    if duplicates not in _DUPLICATES:
+        raise ValueError(f"unknown duplicates {duplicates!r}")
+    b, d = zimg.shape
+    n = ztxt.shape[0]
+    if b < 1 or n < 1:
+        raise RuntimeError("sigmoid_ids needs a non-empty block")
+    dev = zimg.device
+    for what, ids, length in (("img_ids", img_ids, b), ("txt_ids", txt_ids, n)):
+        if (not isinstance(ids, torch.Tensor) or ids.device != dev
+                or ids.dtype != torch.int64 or ids.shape != (length,)
+                or not ids.is_contiguous()):
+            raise RuntimeError(
+                f"{what} must be a contiguous int64 ({length},) tensor on "
+                f"{dev} (got {getattr(ids, 'dtype', type(ids))} "
+                f"{tuple(getattr(ids, 'shape', ()))} on "
+                f"{getattr(ids, 'device', None)})")
+    if not want_g:
+        if g is not None:
+            raise RuntimeError("g given with want_g=False")
+    elif g is None:
+        g = torch.empty((b, n), device=dev, dtype=torch.bfloat16)
+    elif (g.device != dev or g.dtype != torch.bfloat16 or g.shape != (b, n)
+          or g.stride(1) != 1 or (b > 1 and g.stride(0) < n)):
+        raise RuntimeError(
+            f"g must be a bf16 ({b}, {n}) view with unit column stride on "
+            f"{dev} (got {g.dtype} {tuple(g.shape)}, strides "
+            f"{tuple(g.stride())} on {g.device})")
+    lib = _require_lib()
+    tile = lib.sigmoid_ids_tile_dim()
+    zi, zt = zimg.detach().contiguous(), ztxt.detach().contiguous()
+    tp, bp = _prep_scalar(t_prime, dev), _prep_scalar(bias, dev)
+    partials = torch.empty((-(-b // tile) * -(-n // tile), 3), device=dev,
+                           dtype=torch.float32)
+    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
+    if not -(2 ** 31) < diag < 2 ** 31:
+        diag = _DIAG_NONE       # no positive can lie inside an int32 block
+    ldg = n if g is None else max(g.stride(0), n)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.sigmoid_ids_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(bp),
+        _ptr(img_ids), _ptr(txt_ids), _ptr(g), _ptr(partials), b, n, d,
+        ctypes.c_longlong(ldg), diag, _DUPLICATES[duplicates]),
+        "sigmoid_ids_bf16")
+    return partials, g
 
 
 class _FusedL2Normalize(torch.autograd.Function):

@@ -1,8 +1,8 @@
 """In-tree build of the gfx950 HIP extension.
 
 Compiles ``kernels/siglip_kernels.hip``, ``kernels/wgrad_kernels.hip``,
-``kernels/rank_kernels.hip``, ``kernels/softmax_kernels.hip`` and
-``kernels/topk_kernels.hip`` with hipcc into
+``kernels/rank_kernels.hip``, ``kernels/softmax_kernels.hip``,
+``kernels/topk_kernels.hip`` and ``kernels/idlabel_kernels.hip`` with hipcc into
 ``ops/_siglip_hip.so`` (plain C ABI, loaded via ctypes — no torch C++ ABI
 coupling, so a single .so works across torch builds and travels with the
 repo snapshot to GPU boxes).
@@ -22,7 +22,8 @@ _SRCS = [os.path.join(_OPS_DIR, "kernels", "siglip_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "wgrad_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "rank_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "softmax_kernels.hip"),
-         os.path.join(_OPS_DIR, "kernels", "topk_kernels.hip")]
+         os.path.join(_OPS_DIR, "kernels", "topk_kernels.hip"),
+         os.path.join(_OPS_DIR, "kernels", "idlabel_kernels.hip")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

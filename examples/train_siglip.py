@@ -26,6 +26,12 @@ SigLIP initialisation.
 ``--hard-negatives K`` (with ``--eval-every``) adds one line per eval: the
 mean margin between the positive score and the mean of the K hardest negative
 scores, image→text and text→image, over the global batch.
+
+``--captions-per-image C`` trains on multi-caption batches: the batch holds
+``batch-per-gpu / C`` images, each repeated ``C`` times against ``C`` distinct
+texts, and the sample ids (global sample index // C) tell the loss that all
+``C`` pairs of an image are positives.  Needs ``--loss sigmoid --strategy
+all_gather --quant bf16``.
 """
 
 from __future__ import annotations
@@ -87,7 +93,23 @@ def main():
     p.add_argument("--hard-negatives", type=int, default=0,
                    help="with --eval-every: also print the mean margin of "
                         "the positive over the K hardest negatives (0 = off)")
+    p.add_argument("--captions-per-image", type=int, default=1,
+                   help="C texts per image: b/C images repeated C times, "
+                        "positives from sample ids (needs --loss sigmoid "
+                        "--strategy all_gather --quant bf16 and "
+                        "batch-per-gpu %% C == 0)")
     args = p.parse_args()
+    cpi = args.captions_per_image
+    if cpi < 1:
+        p.error("--captions-per-image must be at least 1")
+    if cpi > 1:
+        if (args.loss != "sigmoid" or args.strategy != "all_gather"
+                or args.quant != "bf16"):
+            p.error("--captions-per-image needs --loss sigmoid --strategy "
+                    "all_gather --quant bf16")
+        if args.batch_per_gpu % cpi != 0:
+            p.error("--batch-per-gpu must be a multiple of "
+                    "--captions-per-image")
 
     rank, local_rank, world = init_from_env()
     device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
@@ -111,11 +133,19 @@ def main():
     for step in range(args.steps):
         img, txt = synthetic_batch(args.batch_per_gpu, args.dim, device,
                                    dtype, step * world + rank)
+        ids = None
+        if cpi > 1:
+            # b/C images, each against C distinct texts; an id is the global
+            # sample index // C, so the C pairs of an image share it.
+            img = img[:args.batch_per_gpu // cpi].repeat_interleave(cpi, 0)
+            ids = (rank * args.batch_per_gpu + torch.arange(
+                args.batch_per_gpu, device=device)) // cpi
         opt.zero_grad(set_to_none=True)
         with timer.phase("encode"):
             zi, zt = model(img, txt)
         with timer.phase("loss"):
-            loss = loss_mod(zi, zt)
+            loss = (loss_mod(zi, zt) if ids is None else
+                    loss_mod(zi, zt, image_ids=ids, text_ids=ids))
         with timer.phase("backward"):
             loss.backward()
         with timer.phase("grad_avg"):

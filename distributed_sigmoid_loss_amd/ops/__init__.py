@@ -936,6 +936,55 @@ def siglip_fwd_g(zimg: torch.Tensor, ztxt: torch.Tensor,
     return out3, g_slab, gt_slab if fp8g else None
 
 
+def _pair_block(what: str, zimg: torch.Tensor, ztxt: torch.Tensor):
+    """Validate the embeddings of a pair-grid op ``what``; returns the
+    contiguous detached pair and ``(b, n, d, device)``."""
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings, got "
+            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
+    _validate(zimg, ztxt, "bf16")
+    if ztxt.device != zimg.device:
+        raise RuntimeError("zimg and ztxt must be on the same device")
+    b, d = zimg.shape
+    n = ztxt.shape[0]
+    if b < 1 or n < 1:
+        raise RuntimeError(f"{what} needs a non-empty block")
+    return (zimg.detach().contiguous(), ztxt.detach().contiguous(), b, n, d,
+            zimg.device)
+
+
+def _diag_arg(diag_offset: Optional[int]) -> int:
+    """``diag_offset`` as the kernels' int32 argument."""
+    if diag_offset is None:
+        return _DIAG_NONE
+    diag = int(diag_offset)
+    # No positive can lie inside an int32 block.
+    return diag if -(2 ** 31) < diag < 2 ** 31 else _DIAG_NONE
+
+
+def _g_view(g: Optional[torch.Tensor], b: int, n: int, device):
+    """The dL/dlogit slab of a ``(b, n)`` block, allocated here or the
+    caller's view after validation; returns ``(g, ldg)``."""
+    if g is None:
+        g = torch.empty((b, n), device=device, dtype=torch.bfloat16)
+    elif (g.device != device or g.dtype != torch.bfloat16
+          or g.shape != (b, n) or g.stride(1) != 1
+          or (b > 1 and g.stride(0) < n)):
+        raise RuntimeError(
+            f"g must be a bf16 ({b}, {n}) view with unit column stride on "
+            f"{device} (got {g.dtype} {tuple(g.shape)}, strides "
+            f"{tuple(g.stride())} on {g.device})")
+    return g, max(g.stride(0), n)
+
+
+def _vec_ok(v, dtype, length: int, device) -> bool:
+    """A contiguous ``dtype`` ``(length,)`` tensor on ``device``?"""
+    return (isinstance(v, torch.Tensor) and v.device == device
+            and v.dtype == dtype and v.shape == (length,)
+            and v.is_contiguous())
+
+
 def _rank_side(name: str, thr, cnt, length: int, device):
     """Validate one side (rows or columns) of :func:`pair_rank_counts`;
     returns ``(thr, cnt)`` with ``cnt`` allocated if needed, or
@@ -944,15 +993,13 @@ def _rank_side(name: str, thr, cnt, length: int, device):
         if cnt is not None:
             raise RuntimeError(f"{name}_cnt given without {name}_thr")
         return None, None
-    if (thr.device != device or thr.dtype != torch.float32
-            or thr.shape != (length,) or not thr.is_contiguous()):
+    if not _vec_ok(thr, torch.float32, length, device):
         raise RuntimeError(
             f"{name}_thr must be a contiguous fp32 ({length},) tensor on "
             f"{device} (got {thr.dtype} {tuple(thr.shape)} on {thr.device})")
     if cnt is None:
         cnt = torch.zeros(length, device=device, dtype=torch.int32)
-    elif (cnt.device != device or cnt.dtype != torch.int32
-          or cnt.shape != (length,) or not cnt.is_contiguous()):
+    elif not _vec_ok(cnt, torch.int32, length, device):
         raise RuntimeError(
             f"{name}_cnt must be a contiguous int32 ({length},) tensor on "
             f"{device} (got {cnt.dtype} {tuple(cnt.shape)} on {cnt.device})")
@@ -977,30 +1024,17 @@ def pair_rank_counts(zimg: torch.Tensor, ztxt: torch.Tensor,
     with ``diag_offset − j0``) and repeated calls accumulate; otherwise they
     start from zeros allocated here.  Integer atomics only: the result is
     bitwise reproducible.  No autograd."""
-    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
-        raise RuntimeError(
-            f"expected (b, d) and (n, d) embeddings, got "
-            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
-    _validate(zimg, ztxt, "bf16")
-    if ztxt.device != zimg.device:
-        raise RuntimeError("zimg and ztxt must be on the same device")
-    b, d = zimg.shape
-    n = ztxt.shape[0]
-    if b < 1 or n < 1:
-        raise RuntimeError("pair_rank_counts needs a non-empty block")
+    zi, zt, b, n, d, dev = _pair_block("pair_rank_counts", zimg, ztxt)
     lib = _require_lib()
-    zi, zt = zimg.detach().contiguous(), ztxt.detach().contiguous()
-    row_thr, row_cnt = _rank_side("row", row_thr, row_cnt, b, zi.device)
-    col_thr, col_cnt = _rank_side("col", col_thr, col_cnt, n, zi.device)
+    row_thr, row_cnt = _rank_side("row", row_thr, row_cnt, b, dev)
+    col_thr, col_cnt = _rank_side("col", col_thr, col_cnt, n, dev)
     if row_thr is None and col_thr is None:
         return None, None
-    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
-    if not -(2 ** 31) < diag < 2 ** 31:
-        diag = _DIAG_NONE       # no positive can lie inside an int32 block
-    stream = torch.cuda.current_stream(zi.device).cuda_stream
+    stream = torch.cuda.current_stream(dev).cuda_stream
     _check(lib.pair_rank_counts_bf16(
         ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(row_thr),
-        _ptr(col_thr), _ptr(row_cnt), _ptr(col_cnt), b, n, d, diag),
+        _ptr(col_thr), _ptr(row_cnt), _ptr(col_cnt), b, n, d,
+        _diag_arg(diag_offset)),
         "pair_rank_counts_bf16")
     return row_cnt, col_cnt
 
@@ -1029,34 +1063,19 @@ def pair_topk(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
     workgroups per CU and is clamped to ``[1, ceil(n / tile)]``; the order
     is total, so the result does not depend on it and is bitwise
     reproducible.  No atomics, no autograd."""
-    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
-        raise RuntimeError(
-            f"expected (b, d) and (n, d) embeddings, got "
-            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
-    _validate(zimg, ztxt, "bf16")
-    if ztxt.device != zimg.device:
-        raise RuntimeError("zimg and ztxt must be on the same device")
-    b, d = zimg.shape
-    n = ztxt.shape[0]
-    if b < 1 or n < 1:
-        raise RuntimeError("pair_topk needs a non-empty block")
+    zi, zt, b, n, d, dev = _pair_block("pair_topk", zimg, ztxt)
     lib = _require_lib()
     k = int(k)
     if not 1 <= k <= lib.pair_topk_max_k():
         raise RuntimeError(
             f"pair_topk serves 1 <= k <= {lib.pair_topk_max_k()} (got {k}); "
             "pass impl='torch' for more")
-    zi, zt = zimg.detach().contiguous(), ztxt.detach().contiguous()
-    dev = zi.device
     tile = lib.pair_topk_tile_dim()
     tiles_m, tiles_n = -(-b // tile), -(-n // tile)
     if n_splits is None:
         n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
         n_splits = -(-2 * n_cu // tiles_m)
     n_splits = max(1, min(int(n_splits), tiles_n))
-    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
-    if not -(2 ** 31) < diag < 2 ** 31:
-        diag = _DIAG_NONE       # no positive can lie inside an int32 block
     cap = lib.pair_topk_capacity(k)
     ws_s = torch.empty((n_splits, b, cap), device=dev, dtype=torch.float32)
     ws_c = torch.empty((n_splits, b, cap), device=dev, dtype=torch.int32)
@@ -1065,7 +1084,8 @@ def pair_topk(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
     stream = torch.cuda.current_stream(dev).cuda_stream
     _check(lib.pair_topk_bf16(
         ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(ws_s), _ptr(ws_c),
-        _ptr(out_s), _ptr(out_c), b, n, d, diag, k, n_splits),
+        _ptr(out_s), _ptr(out_c), b, n, d, _diag_arg(diag_offset), k,
+        n_splits),
         "pair_topk_bf16")
     return out_s, out_c
 
@@ -1074,19 +1094,9 @@ def _softmax_block(what: str, zimg: torch.Tensor, ztxt: torch.Tensor,
                    t_prime: torch.Tensor):
     """Validate the embeddings of a softmax op; returns the contiguous
     detached pair, ``t'`` as a device fp32 scalar and the tile counts."""
-    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
-        raise RuntimeError(
-            f"expected (b, d) and (n, d) embeddings, got "
-            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
-    _validate(zimg, ztxt, "bf16")
-    if ztxt.device != zimg.device:
-        raise RuntimeError("zimg and ztxt must be on the same device")
-    b, n = zimg.shape[0], ztxt.shape[0]
-    if b < 1 or n < 1:
-        raise RuntimeError(f"{what} needs a non-empty block")
+    zi, zt, b, n, _, dev = _pair_block(what, zimg, ztxt)
     tile = _require_lib().softmax_tile_dim()
-    return (zimg.detach().contiguous(), ztxt.detach().contiguous(),
-            _prep_scalar(t_prime, zimg.device), -(-b // tile), -(-n // tile))
+    return zi, zt, _prep_scalar(t_prime, dev), -(-b // tile), -(-n // tile)
 
 
 def _softmax_side(name: str, lse, w, length: int, device):
@@ -1095,9 +1105,7 @@ def _softmax_side(name: str, lse, w, length: int, device):
     if (lse is None) != (w is None):
         raise RuntimeError(f"{name}_lse and {name}_w must be given together")
     for what, v in ((f"{name}_lse", lse), (f"{name}_w", w)):
-        if v is not None and (
-                v.device != device or v.dtype != torch.float32
-                or v.shape != (length,) or not v.is_contiguous()):
+        if v is not None and not _vec_ok(v, torch.float32, length, device):
             raise RuntimeError(
                 f"{what} must be a contiguous fp32 ({length},) tensor on "
                 f"{device} (got {v.dtype} {tuple(v.shape)} on {v.device})")
@@ -1170,23 +1178,13 @@ def softmax_g(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
     dev = zi.device
     row_lse, row_w = _softmax_side("row", row_lse, row_w, b, dev)
     col_lse, col_w = _softmax_side("col", col_lse, col_w, n, dev)
-    if g is None:
-        g = torch.empty((b, n), device=dev, dtype=torch.bfloat16)
-    elif (g.device != dev or g.dtype != torch.bfloat16 or g.shape != (b, n)
-          or g.stride(1) != 1 or (b > 1 and g.stride(0) < n)):
-        raise RuntimeError(
-            f"g must be a bf16 ({b}, {n}) view with unit column stride on "
-            f"{dev} (got {g.dtype} {tuple(g.shape)}, strides "
-            f"{tuple(g.stride())} on {g.device})")
+    g, ldg = _g_view(g, b, n, dev)
     gs = torch.empty(tiles_m * tiles_n, device=dev, dtype=torch.float32)
-    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
-    if not -(2 ** 31) < diag < 2 ** 31:
-        diag = _DIAG_NONE       # no positive can lie inside an int32 block
     stream = torch.cuda.current_stream(dev).cuda_stream
     _check(lib.softmax_g_bf16(
         ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(row_lse),
         _ptr(row_w), _ptr(col_lse), _ptr(col_w), _ptr(g), _ptr(gs), b, n, d,
-        ctypes.c_longlong(max(g.stride(0), n)), diag), "softmax_g_bf16")
+        ctypes.c_longlong(ldg), _diag_arg(diag_offset)), "softmax_g_bf16")
     return g, gs
 
 
@@ -1219,55 +1217,32 @@ def sigmoid_ids(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
     offset and its row stride, so slicing, not pointer arithmetic, bounds the
     write; only its elements are touched.  ``t_prime`` and ``bias`` are read
     on the device (no host sync).  No autograd."""
-    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
-        raise RuntimeError(
-            f"expected (b, d) and (n, d) embeddings, got "
-            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
-    _validate(zimg, ztxt, "bf16")
-    if ztxt.device != zimg.device:
-        raise RuntimeError("zimg and ztxt must be on the same device")
+    zi, zt, b, n, d, dev = _pair_block("sigmoid_ids", zimg, ztxt)
     if duplicates not in _DUPLICATES:
         raise ValueError(f"unknown duplicates {duplicates!r}")
-    b, d = zimg.shape
-    n = ztxt.shape[0]
-    if b < 1 or n < 1:
-        raise RuntimeError("sigmoid_ids needs a non-empty block")
-    dev = zimg.device
     for what, ids, length in (("img_ids", img_ids, b), ("txt_ids", txt_ids, n)):
-        if (not isinstance(ids, torch.Tensor) or ids.device != dev
-                or ids.dtype != torch.int64 or ids.shape != (length,)
-                or not ids.is_contiguous()):
+        if not _vec_ok(ids, torch.int64, length, dev):
             raise RuntimeError(
                 f"{what} must be a contiguous int64 ({length},) tensor on "
                 f"{dev} (got {getattr(ids, 'dtype', type(ids))} "
                 f"{tuple(getattr(ids, 'shape', ()))} on "
                 f"{getattr(ids, 'device', None)})")
-    if not want_g:
-        if g is not None:
-            raise RuntimeError("g given with want_g=False")
-    elif g is None:
-        g = torch.empty((b, n), device=dev, dtype=torch.bfloat16)
-    elif (g.device != dev or g.dtype != torch.bfloat16 or g.shape != (b, n)
-          or g.stride(1) != 1 or (b > 1 and g.stride(0) < n)):
-        raise RuntimeError(
-            f"g must be a bf16 ({b}, {n}) view with unit column stride on "
-            f"{dev} (got {g.dtype} {tuple(g.shape)}, strides "
-            f"{tuple(g.stride())} on {g.device})")
+    ldg = n
+    if want_g:
+        g, ldg = _g_view(g, b, n, dev)
+    elif g is not None:
+        raise RuntimeError("g given with want_g=False")
     lib = _require_lib()
     tile = lib.sigmoid_ids_tile_dim()
-    zi, zt = zimg.detach().contiguous(), ztxt.detach().contiguous()
     tp, bp = _prep_scalar(t_prime, dev), _prep_scalar(bias, dev)
     partials = torch.empty((-(-b // tile) * -(-n // tile), 3), device=dev,
                            dtype=torch.float32)
-    diag = _DIAG_NONE if diag_offset is None else int(diag_offset)
-    if not -(2 ** 31) < diag < 2 ** 31:
-        diag = _DIAG_NONE       # no positive can lie inside an int32 block
-    ldg = n if g is None else max(g.stride(0), n)
     stream = torch.cuda.current_stream(dev).cuda_stream
     _check(lib.sigmoid_ids_bf16(
         ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(bp),
         _ptr(img_ids), _ptr(txt_ids), _ptr(g), _ptr(partials), b, n, d,
-        ctypes.c_longlong(ldg), diag, _DUPLICATES[duplicates]),
+        ctypes.c_longlong(ldg), _diag_arg(diag_offset),
+        _DUPLICATES[duplicates]),
         "sigmoid_ids_bf16")
     return partials, g
 

@@ -5,13 +5,16 @@ Compiles ``kernels/siglip_kernels.hip``, ``kernels/wgrad_kernels.hip``,
 ``kernels/topk_kernels.hip`` and ``kernels/idlabel_kernels.hip`` with hipcc into
 ``ops/_siglip_hip.so`` (plain C ABI, loaded via ctypes — no torch C++ ABI
 coupling, so a single .so works across torch builds and travels with the
-repo snapshot to GPU boxes).
+repo snapshot to GPU boxes).  The last four include ``kernels/pair_tile.h``,
+which sits next to them and needs no include flag; the extension is rebuilt
+when a source or any header under ``kernels/`` is newer than the ``.so``.
 
 Usage:  python -m distributed_sigmoid_loss_amd.ops.build
 """
 
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -29,11 +32,18 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 
+def _deps() -> list:
+    """What the extension is built from: the sources and every header next to
+    them."""
+    kernels = os.path.dirname(_SRCS[0])
+    return _SRCS + sorted(glob.glob(os.path.join(kernels, "*.h")))
+
+
 def _stale() -> bool:
     if not os.path.exists(SO_PATH):
         return True
     so_mtime = os.path.getmtime(SO_PATH)
-    return any(os.path.getmtime(s) > so_mtime for s in _SRCS)
+    return any(os.path.getmtime(s) > so_mtime for s in _deps())
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -24,20 +24,10 @@
 // There is no floating-point atomic anywhere: every reduction has a fixed
 // order, so all results are bitwise reproducible.
 //
-// Structure (the rank kernel's tile).  128×128 output tile per 256-thread
-// workgroup, 4 waves as 2 (M) × 2 (N), 64×64 (4×4 fragments of
-// v_mfma_f32_16x16x32_bf16) each, fp32 accumulation.  A k-step stages a
-// [128 rows][64 k] slab of each operand in LDS (double-buffered, 2 × 32 KiB)
-// through registers with 16-byte loads; rows past b / n and k past d are
-// zero-filled, so one kernel serves interior and ragged tiles.  The 16-byte
-// chunk index is XOR-ed with (row >> 1) & 7, which makes a fragment's
-// ds_read_b128 conflict-free.  Two workgroups (64 KiB each) share a CU.
-//
-// The MFMA operands are exchanged (text fragment first), so the accumulator
-// holds the transposed 16×16 block: lane l owns image row (l & 15) and the
-// four consecutive text columns 4·(l >> 4) … +3.  A lane's g values are then
-// contiguous in the output row (one 8-byte LDS write per fragment), and a row
-// reduction needs 2 shuffles where a column reduction needs 4.
+// Structure.  The tile, its main loop (text fragment first: lane l owns image
+// row (l & 15) and four consecutive text columns of each fragment, so its g
+// values are one 8-byte LDS write per fragment), the block walk and the g
+// write-out are pair_tile.h's; this file adds the epilogues.
 //
 // Padding.  A zero-filled padding column scores z = 0, which would dominate a
 // row of negative logits: every element outside the block is replaced by
@@ -46,167 +36,12 @@
 //
 // exp / log are the bare v_exp_f32 / v_log_f32 (base 2) with the ln 2 factors
 // folded into the scale of the argument and of the result.
-//
-// Placement.  One workgroup per tile on a 1-D grid; the block id is remapped
-// so consecutive logical ids share an XCD, and logical ids walk the tile grid
-// in groups of 8 tile-rows, column by column.
 
-#include <hip/hip_runtime.h>
-#include <climits>
-#include <cstdint>
+#include "pair_tile.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-constexpr int BM = 128;          // image rows per tile
-constexpr int BN = 128;          // text rows (logit columns) per tile
-constexpr int BK = 64;           // k per step: one 128-byte LDS row
-constexpr int NTHREADS = 256;    // 4 waves as 2 (M) × 2 (N), 64×64 each
-constexpr int ROW_BYTES = 2 * BK;
-constexpr int OP_BYTES = BM * ROW_BYTES;      // one operand slab: 16 KiB
-constexpr int BUF_BYTES = 2 * OP_BYTES;       // zimg slab + ztxt slab
-constexpr int LOADS = BM * 8 / NTHREADS;      // 16-B chunks per thread: 4
-constexpr int GROUP_M = 8;       // tile-rows per locality group
-constexpr int DIAG_NONE = INT_MIN;
-// g staging tile: 128 rows of 256 B, padded to 272 B (68 dwords ≡ 4 mod 64
-// banks) so the 8-byte writes of lanes (row fr, quad fq) fall on distinct
-// banks within each half-wave.
-constexpr int G_PITCH = 2 * BN + 16;
-constexpr int G_STAGE_BYTES = BM * G_PITCH;   // 34 KiB of the 64 KiB
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
-
 static_assert(G_STAGE_BYTES + 16 <= 2 * BUF_BYTES, "g staging exceeds LDS");
-
-inline int ceil_div(int a, int b) { return (a - 1) / b + 1; }  // a ≥ 1
-
-// Byte offset of 16-byte chunk `ch` (0..7) of row `row` in an operand slab.
-__device__ __forceinline__ int lds_off(int row, int ch) {
-  return ROW_BYTES * row + 16 * (ch ^ ((row >> 1) & 7));
-}
-
-struct TilePos { int tm, tn; };
-
-// XCD-contiguous (bijective) remap, then the grouped column-major walk.
-__device__ __forceinline__ TilePos tile_of_block(int tiles_m, int tiles_n) {
-  const int nwg = tiles_m * tiles_n;
-  const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3);
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8)
-                  + slot;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = lid / per_group;
-  const int first_m = group * GROUP_M;
-  const int group_h = (tiles_m - first_m < GROUP_M) ? tiles_m - first_m
-                                                    : GROUP_M;
-  const int in_group = lid - group * per_group;
-  return TilePos{first_m + in_group % group_h, in_group / group_h};
-}
-
-// acc[i][j][r] = <zimg row m0 + wm·64 + i·16 + (lane & 15),
-//                 ztxt row n0 + wn·64 + j·16 + 4·(lane >> 4) + r>
-// (0 where either row lies outside its matrix).  Ends on a barrier: every
-// read of the staging buffers has retired, the caller may reuse `lds`.
-__device__ __forceinline__ void pair_tile_dots(
-    const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt, int b,
-    int n, int d, int m0, int n0, unsigned char* lds, f32x4 (&acc)[4][4]) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-
-  // Staging: thread t owns chunk t&7 of rows (t>>3) + 32·i, i = 0..3.
-  const int ld_ch = tid & 7;
-  const int ld_row = tid >> 3;
-  const __bf16* a_src[LOADS];
-  const __bf16* b_src[LOADS];
-  bool a_ok[LOADS], b_ok[LOADS];
-  int st_off[LOADS];
-#pragma unroll
-  for (int i = 0; i < LOADS; ++i) {
-    const int row = ld_row + 32 * i;
-    a_ok[i] = m0 + row < b;
-    b_ok[i] = n0 + row < n;
-    a_src[i] = zimg + (long long)(m0 + row) * d + ld_ch * 8;
-    b_src[i] = ztxt + (long long)(n0 + row) * d + ld_ch * 8;
-    st_off[i] = lds_off(row, ld_ch);
-  }
-
-  // Fragment reads: lane l takes row (l & 15), k = 8·(l >> 4) … +7 of each
-  // 32-deep MFMA step, i.e. chunk 4·kk + (l >> 4).
-  const int fr = lane & 15, fq = lane >> 4;
-  int a_off[4][2], b_off[4][2];
-#pragma unroll
-  for (int f = 0; f < 4; ++f)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      a_off[f][kk] = lds_off(wm * 64 + f * 16 + fr, 4 * kk + fq);
-      b_off[f][kk] = OP_BYTES + lds_off(wn * 64 + f * 16 + fr, 4 * kk + fq);
-    }
-
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  uint4 ra[LOADS], rb[LOADS];
-
-  auto load_step = [&](int s) {
-    const int k0 = s * BK;
-    const bool k_ok = k0 + ld_ch * 8 < d;     // d % 8 == 0: all or nothing
-#pragma unroll
-    for (int i = 0; i < LOADS; ++i) {
-      ra[i] = uint4{0u, 0u, 0u, 0u};
-      rb[i] = uint4{0u, 0u, 0u, 0u};
-      if (k_ok && a_ok[i])
-        ra[i] = *reinterpret_cast<const uint4*>(a_src[i] + k0);
-      if (k_ok && b_ok[i])
-        rb[i] = *reinterpret_cast<const uint4*>(b_src[i] + k0);
-    }
-  };
-  auto store_step = [&](int buf) {
-    unsigned char* base = lds + buf * BUF_BYTES;
-#pragma unroll
-    for (int i = 0; i < LOADS; ++i) {
-      *reinterpret_cast<uint4*>(base + st_off[i]) = ra[i];
-      *reinterpret_cast<uint4*>(base + OP_BYTES + st_off[i]) = rb[i];
-    }
-  };
-
-  const int nsteps = (d + BK - 1) / BK;
-  load_step(0);
-  store_step(0);
-  __syncthreads();
-
-  for (int s = 0; s < nsteps; ++s) {
-    const bool more = s + 1 < nsteps;
-    if (more) load_step(s + 1);
-
-    const unsigned char* base = lds + (s & 1) * BUF_BYTES;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 af[4], bfr[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        af[f] = *reinterpret_cast<const bf16x8*>(base + a_off[f][kk]);
-        bfr[f] = *reinterpret_cast<const bf16x8*>(base + b_off[f][kk]);
-      }
-      // Text fragment first: the accumulator is the transposed block.
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              bfr[j], af[i], acc[i][j], 0, 0, 0);
-    }
-
-    if (more) store_step((s + 1) & 1);
-    __syncthreads();
-  }
-}
 
 // exp(x − m) terms of a log-sum-exp in base 2: `sc2` is t·log2 e, `m` a raw
 // dot product; m == −inf (nothing valid) is replaced by 0 so that the
@@ -221,11 +56,12 @@ __launch_bounds__(NTHREADS) __global__ void softmax_lse_partials_kernel(
     float2* __restrict__ col_ws, int b, int n, int d, int tiles_m,
     int tiles_n) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
+  static_assert(sizeof(lds) >= 2 * BUF_BYTES, "staging buffers exceed the LDS");
 
   const TilePos tp = tile_of_block(tiles_m, tiles_n);
   const int m0 = tp.tm * BM, n0 = tp.tn * BN;
   f32x4 acc[4][4];
-  pair_tile_dots(zimg, ztxt, b, n, d, m0, n0, lds, acc);
+  pair_tile_dots<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -359,11 +195,12 @@ __launch_bounds__(NTHREADS) __global__ void softmax_g_kernel(
     float* __restrict__ gs_ws, int b, int n, int d, long long ldg, int diag,
     int tiles_m, int tiles_n) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
+  static_assert(sizeof(lds) >= 2 * BUF_BYTES, "staging buffers exceed the LDS");
 
   const TilePos tp = tile_of_block(tiles_m, tiles_n);
   const int m0 = tp.tm * BM, n0 = tp.tn * BN;
   f32x4 acc[4][4];
-  pair_tile_dots(zimg, ztxt, b, n, d, m0, n0, lds, acc);
+  pair_tile_dots<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -394,9 +231,7 @@ __launch_bounds__(NTHREADS) __global__ void softmax_g_kernel(
     const bool row_ok = row < b;
     const float rl2 = (rows_on && row_ok) ? -row_lse[row] * LOG2E : 0.f;
     const float rw = (rows_on && row_ok) ? row_w[row] : 0.f;
-    // Column of this row's positive, −1 when there is none in the block.
-    const long long pos = (long long)row + diag;
-    const int pc = (diag != DIAG_NONE && pos >= 0 && pos < n) ? (int)pos : -1;
+    const int pc = positive_col(row, diag, n);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int col0 = n0 + wn * 64 + j * 16 + fq * 4;
@@ -431,38 +266,16 @@ __launch_bounds__(NTHREADS) __global__ void softmax_g_kernel(
     gs_ws[(long long)tp.tm * tiles_n + tp.tn] =
         ((red[0] + red[1]) + red[2]) + red[3];
 
-  // Write-out: 16 threads cover one 256-byte tile row.  A 16-byte store
-  // where the segment is whole and its address aligned, 2-byte stores
-  // otherwise (ragged edge, odd row stride or column offset).
-  const int ch = tid & 15;
-#pragma unroll
-  for (int k = 0; k < BM / 16; ++k) {
-    const int lrow = (tid >> 4) + 16 * k;
-    const int row = m0 + lrow, col = n0 + ch * 8;
-    if (row >= b || col >= n) continue;
-    const uint4 v =
-        *reinterpret_cast<const uint4*>(lds + lrow * G_PITCH + 16 * ch);
-    __bf16* dst = g + (long long)row * ldg + col;
-    if (col + 8 <= n && ((uintptr_t)dst & 15) == 0) {
-      *reinterpret_cast<uint4*>(dst) = v;
-    } else {
-      const unsigned short* h = reinterpret_cast<const unsigned short*>(&v);
-      unsigned short* dst16 = reinterpret_cast<unsigned short*>(dst);
-#pragma unroll
-      for (int x = 0; x < 8; ++x)
-        if (col + x < n) dst16[x] = h[x];
-    }
-  }
+  store_g_tile(lds, g, ldg, m0, n0, b, n);
 }
 
+// The embedding checks plus what both entries add: t' and the grid size.
 bool dims_ok(const void* zimg, const void* ztxt, const void* tprime, int b,
              int n, int d) {
-  if (zimg == nullptr || ztxt == nullptr || tprime == nullptr) return false;
-  if (b < 1 || n < 1 || d < 8 || d % 8 != 0) return false;
-  if (((uintptr_t)zimg | (uintptr_t)ztxt) % 16 != 0 ||
+  if (!pair_dims_ok(zimg, ztxt, b, n, d) || tprime == nullptr ||
       (uintptr_t)tprime % 4 != 0)
     return false;
-  return (long long)ceil_div(b, BM) * ceil_div(n, BN) < (1ll << 31);
+  return pair_grid_ok(ceil_div(b, BM), ceil_div(n, BN));
 }
 
 }  // namespace

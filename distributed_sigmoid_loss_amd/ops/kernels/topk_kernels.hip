@@ -17,21 +17,16 @@
 //
 // - pair_topk_partials_kernel<KCAP>: a workgroup owns 128 image rows and split
 //   `s` of `n_splits`, a contiguous span of 128-column tiles that it walks in
-//   ascending order.  Every tile is the rank kernel's 128×128 MFMA tile with
-//   the operands exchanged as in softmax_kernels.hip; the epilogue below folds
-//   it into a running sorted list of KCAP (score, column) pairs per row.  After
-//   the last tile the lists go to a workspace laid out (n_splits, b, KCAP).
+//   ascending order.  Every tile is pair_tile.h's 128×128 MFMA tile with the
+//   text fragment first; the epilogue below folds it into a running sorted
+//   list of KCAP (score, column) pairs per row.  After the last tile the
+//   lists go to a workspace laid out (n_splits, b, KCAP).
 // - pair_topk_merge_kernel<KCAP>: one thread per row folds the row's n_splits
 //   workspace lists, in split order, into one list under the same total order
 //   and writes its first k entries, the (−inf, −1) fill included.
 //
-// Tile (the rank kernel's).  256 threads, 4 waves as 2 (M) × 2 (N), 64×64
-// (4×4 fragments of v_mfma_f32_16x16x32_bf16) each, fp32 accumulation; a
-// k-step stages a [128 rows][64 k] slab of each operand in LDS
-// (double-buffered, 2 × 32 KiB) through registers with 16-byte loads, rows
-// past b / n and k past d zero-filled; the 16-byte chunk index is XOR-ed with
-// (row >> 1) & 7.  With the text fragment first, lane l owns image row
-// (l & 15) and the four consecutive columns 4·(l >> 4) … +3 of each fragment.
+// Tile.  pair_tile.h's, text fragment first: lane l owns image row (l & 15)
+// and the four consecutive columns 4·(l >> 4) … +3 of each fragment.
 //
 // Epilogue: a per-row threshold.  thr[row] (LDS) is the score of the row's
 // current KCAP-th entry, −inf while the list is not full.  Each lane compares
@@ -59,24 +54,10 @@
 // tile-row l / n_splits and split l % n_splits: the splits of a tile-row sit
 // on one XCD and share its image panel in L2.
 
-#include <hip/hip_runtime.h>
-#include <climits>
-#include <cstdint>
+#include "pair_tile.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-constexpr int BM = 128;          // image rows per tile
-constexpr int BN = 128;          // text rows (score columns) per tile
-constexpr int BK = 64;           // k per step: one 128-byte LDS row
-constexpr int NTHREADS = 256;    // 4 waves as 2 (M) × 2 (N), 64×64 each
-constexpr int ROW_BYTES = 2 * BK;
-constexpr int OP_BYTES = BM * ROW_BYTES;      // one operand slab: 16 KiB
-constexpr int BUF_BYTES = 2 * OP_BYTES;       // zimg slab + ztxt slab
-constexpr int LOADS = BM * 8 / NTHREADS;      // 16-B chunks per thread: 4
-constexpr int DIAG_NONE = INT_MIN;
 constexpr int MAX_K = 16;        // largest compiled list capacity
 
 // Candidate buffer: [128][128] fp32 at a pitch of 129, so that the fold's
@@ -86,115 +67,6 @@ constexpr int CAND_PITCH = BN + 1;
 constexpr int LDS_BYTES = BM * CAND_PITCH * 4;
 
 static_assert(LDS_BYTES >= 2 * BUF_BYTES, "staging buffers exceed the LDS");
-
-inline int ceil_div(int a, int b) { return (a - 1) / b + 1; }  // a ≥ 1
-
-// Byte offset of 16-byte chunk `ch` (0..7) of row `row` in an operand slab.
-__device__ __forceinline__ int lds_off(int row, int ch) {
-  return ROW_BYTES * row + 16 * (ch ^ ((row >> 1) & 7));
-}
-
-// acc[i][j][r] = <zimg row m0 + wm·64 + i·16 + (lane & 15),
-//                 ztxt row n0 + wn·64 + j·16 + 4·(lane >> 4) + r>
-// (0 where either row lies outside its matrix).  Ends on a barrier: every
-// read of the staging buffers has retired, the caller may reuse `lds`.
-__device__ __forceinline__ void pair_tile_dots(
-    const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt, int b,
-    int n, int d, int m0, int n0, unsigned char* lds, f32x4 (&acc)[4][4]) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-
-  // Staging: thread t owns chunk t&7 of rows (t>>3) + 32·i, i = 0..3.
-  const int ld_ch = tid & 7;
-  const int ld_row = tid >> 3;
-  const __bf16* a_src[LOADS];
-  const __bf16* b_src[LOADS];
-  bool a_ok[LOADS], b_ok[LOADS];
-  int st_off[LOADS];
-#pragma unroll
-  for (int i = 0; i < LOADS; ++i) {
-    const int row = ld_row + 32 * i;
-    a_ok[i] = m0 + row < b;
-    b_ok[i] = n0 + row < n;
-    a_src[i] = zimg + (long long)(m0 + row) * d + ld_ch * 8;
-    b_src[i] = ztxt + (long long)(n0 + row) * d + ld_ch * 8;
-    st_off[i] = lds_off(row, ld_ch);
-  }
-
-  // Fragment reads: lane l takes row (l & 15), k = 8·(l >> 4) … +7 of each
-  // 32-deep MFMA step, i.e. chunk 4·kk + (l >> 4).
-  const int fr = lane & 15, fq = lane >> 4;
-  int a_off[4][2], b_off[4][2];
-#pragma unroll
-  for (int f = 0; f < 4; ++f)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      a_off[f][kk] = lds_off(wm * 64 + f * 16 + fr, 4 * kk + fq);
-      b_off[f][kk] = OP_BYTES + lds_off(wn * 64 + f * 16 + fr, 4 * kk + fq);
-    }
-
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  uint4 ra[LOADS], rb[LOADS];
-
-  auto load_step = [&](int s) {
-    const int k0 = s * BK;
-    const bool k_ok = k0 + ld_ch * 8 < d;     // d % 8 == 0: all or nothing
-#pragma unroll
-    for (int i = 0; i < LOADS; ++i) {
-      ra[i] = uint4{0u, 0u, 0u, 0u};
-      rb[i] = uint4{0u, 0u, 0u, 0u};
-      if (k_ok && a_ok[i])
-        ra[i] = *reinterpret_cast<const uint4*>(a_src[i] + k0);
-      if (k_ok && b_ok[i])
-        rb[i] = *reinterpret_cast<const uint4*>(b_src[i] + k0);
-    }
-  };
-  auto store_step = [&](int buf) {
-    unsigned char* base = lds + buf * BUF_BYTES;
-#pragma unroll
-    for (int i = 0; i < LOADS; ++i) {
-      *reinterpret_cast<uint4*>(base + st_off[i]) = ra[i];
-      *reinterpret_cast<uint4*>(base + OP_BYTES + st_off[i]) = rb[i];
-    }
-  };
-
-  const int nsteps = (d + BK - 1) / BK;
-  load_step(0);
-  store_step(0);
-  __syncthreads();
-
-  for (int s = 0; s < nsteps; ++s) {
-    const bool more = s + 1 < nsteps;
-    if (more) load_step(s + 1);
-
-    const unsigned char* base = lds + (s & 1) * BUF_BYTES;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 af[4], bfr[4];
-#pragma unroll
-      for (int f = 0; f < 4; ++f) {
-        af[f] = *reinterpret_cast<const bf16x8*>(base + a_off[f][kk]);
-        bfr[f] = *reinterpret_cast<const bf16x8*>(base + b_off[f][kk]);
-      }
-      // Text fragment first: the accumulator is the transposed block.
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              bfr[j], af[i], acc[i][j], 0, 0, 0);
-    }
-
-    if (more) store_step((s + 1) & 1);
-    __syncthreads();
-  }
-}
 
 // A row's running list, best first.  All indices are compile-time constants
 // after unrolling, so the list stays in registers.
@@ -242,11 +114,7 @@ __launch_bounds__(NTHREADS) __global__ void pair_topk_partials_kernel(
   __shared__ float thr[BM];
 
   // XCD-contiguous (bijective) remap; splits of a tile-row are neighbours.
-  const int nwg = tiles_m * n_splits;
-  const int xcd = (int)(blockIdx.x & 7), slot = (int)(blockIdx.x >> 3);
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8)
-                  + slot;
+  const int lid = xcd_logical_id(tiles_m * n_splits);
   const int tm = lid / n_splits, split = lid - tm * n_splits;
   const int m0 = tm * BM;
   // Split s owns column tiles [s·T/S, (s+1)·T/S): never empty as S ≤ T.
@@ -268,8 +136,7 @@ __launch_bounds__(NTHREADS) __global__ void pair_topk_partials_kernel(
   for (int i = 0; i < 4; ++i) {
     const int row = m0 + wm * 64 + i * 16 + fr;
     row_ok[i] = row < b;
-    const long long pos = (long long)row + diag;
-    pc[i] = (diag != DIAG_NONE && pos >= 0 && pos < n) ? (int)pos : -1;
+    pc[i] = positive_col(row, diag, n);
   }
 
   TopList<KCAP> top;             // used by threads 0..127: row m0 + tid
@@ -280,7 +147,7 @@ __launch_bounds__(NTHREADS) __global__ void pair_topk_partials_kernel(
   for (int tn = t_begin; tn < t_end; ++tn) {
     const int n0 = tn * BN;
     f32x4 acc[4][4];
-    pair_tile_dots(zimg, ztxt, b, n, d, m0, n0, lds, acc);
+    pair_tile_dots<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
 
     // Candidates: score to the element's slot, bit 4·j + r to the lane mask.
 #pragma unroll
@@ -430,20 +297,17 @@ int pair_topk_capacity(int k) { return capacity_for(k); }
 int pair_topk_bf16(uintptr_t stream, const void* zimg, const void* ztxt,
                    void* ws_s, void* ws_c, void* out_s, void* out_c, int b,
                    int n, int d, int diag, int k, int n_splits) {
-  if (zimg == nullptr || ztxt == nullptr || ws_s == nullptr ||
+  if (!pair_dims_ok(zimg, ztxt, b, n, d) || ws_s == nullptr ||
       ws_c == nullptr || out_s == nullptr || out_c == nullptr)
-    return (int)hipErrorInvalidValue;
-  if (b < 1 || n < 1 || d < 8 || d % 8 != 0)
     return (int)hipErrorInvalidValue;
   const int kcap = capacity_for(k);
   if (kcap == 0) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)zimg | (uintptr_t)ztxt) % 16 != 0 ||
-      ((uintptr_t)ws_s | (uintptr_t)ws_c | (uintptr_t)out_s |
+  if (((uintptr_t)ws_s | (uintptr_t)ws_c | (uintptr_t)out_s |
        (uintptr_t)out_c) % 4 != 0)
     return (int)hipErrorInvalidValue;
   const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
   if (n_splits < 1 || n_splits > tiles_n ||
-      (long long)tiles_m * n_splits >= (1ll << 31))
+      !pair_grid_ok(tiles_m, n_splits))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
 #define TOPK_LAUNCH(KCAP)                                                     \

@@ -32,6 +32,11 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
   captions per image, repeated samples, padding rows), from a fused HIP kernel
   with a saved-g and a band-recompute backward; ``DistributedSigmoidLoss``
   takes ``image_ids`` / ``text_ids``.
+- ``softmax_contrastive_loss_ids`` — the softmax loss with the same sample-ID
+  labels (multi-positive InfoNCE: the mean over a row's or column's positives
+  of ``−log softmax``, masked pairs out of both normalisers), from a fused
+  HIP kernel pair that adds positive sums and counts to the log-sum-exp pass;
+  ``DistributedSoftmaxLoss`` takes ``image_ids`` / ``text_ids``.
 
 The compute path is PyTorch-ROCm + HIP/CDNA4 kernels + RCCL over xGMI; there
 are no CUDA compatibility layers and no multi-backend dispatch.
@@ -57,6 +62,7 @@ from .losses.retrieval import (
 from .losses.softmax_loss import (
     DistributedSoftmaxLoss,
     softmax_contrastive_loss,
+    softmax_contrastive_loss_ids,
 )
 from .losses.id_labels import sigmoid_contrastive_loss_ids
 from .parallel.ring import (
@@ -84,6 +90,7 @@ __all__ = [
     "distributed_retrieval_topk",
     "DistributedSoftmaxLoss",
     "softmax_contrastive_loss",
+    "softmax_contrastive_loss_ids",
     "sigmoid_contrastive_loss_ids",
     "neighbour_exchange",
     "neighbour_exchange_bidir",

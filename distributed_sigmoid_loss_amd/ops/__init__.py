@@ -41,6 +41,12 @@ exposes:
   per row, duplicates switched off, padding rows), as per-tile
   ``(loss, Σ g·s, Σ g)`` partials plus the optional dL/dlogit slab
   (``losses/id_labels.py`` builds the loss and its two backward regimes).
+- sample-ID labels for the softmax loss: :func:`pair_lse_ids` — masked row
+  and column log-sum-exp plus each row's and column's positive-logit sum and
+  positive count — and :func:`softmax_g_ids` — the dL/dlogit slab with
+  several positives per row and masked pairs at exactly 0
+  (``losses/softmax_loss.py`` builds the multi-positive InfoNCE loss on
+  them).
 
 Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
@@ -244,6 +250,24 @@ def _load():
     lib.sigmoid_ids_bf16.restype = ctypes.c_int
     lib.sigmoid_ids_bf16.argtypes = (
         [ctypes.c_void_p] * 9 + [ctypes.c_int] * 3 + [ctypes.c_longlong]
+        + [ctypes.c_int] * 2)
+    if not hasattr(lib, "softmax_ids_lse_bf16"):
+        _lib_err = (f"stale HIP extension at {SO_PATH} (no softmax sample-ID "
+                    "kernels); rebuild with: "
+                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
+        return None
+    lib.softmax_ids_tile_dim.restype = ctypes.c_int
+    lib.softmax_ids_tile_dim.argtypes = []
+    # (stream, zimg, ztxt, t', img_ids, txt_ids, row_ws, col_ws, row_lse,
+    #  row_pos, row_cnt, col_lse, col_pos, col_cnt, b, n, d, diag, mode)
+    lib.softmax_ids_lse_bf16.restype = ctypes.c_int
+    lib.softmax_ids_lse_bf16.argtypes = (
+        [ctypes.c_void_p] * 14 + [ctypes.c_int] * 5)
+    # (stream, zimg, ztxt, t', img_ids, txt_ids, row_lse, row_w, row_pw,
+    #  col_lse, col_w, col_pw, g, gs_ws, b, n, d, ldg, diag, mode)
+    lib.softmax_ids_g_bf16.restype = ctypes.c_int
+    lib.softmax_ids_g_bf16.argtypes = (
+        [ctypes.c_void_p] * 14 + [ctypes.c_int] * 3 + [ctypes.c_longlong]
         + [ctypes.c_int] * 2)
     _lib = lib
     return _lib
@@ -1191,6 +1215,20 @@ def softmax_g(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
 _DUPLICATES = {"positive": 0, "ignore": 1}
 
 
+def _check_id_labels(duplicates, img_ids, txt_ids, b: int, n: int, dev):
+    """What every sample-ID op checks of its labels: a known ``duplicates``
+    mode and contiguous int64 ``(b,)`` / ``(n,)`` ids on ``dev``."""
+    if duplicates not in _DUPLICATES:
+        raise ValueError(f"unknown duplicates {duplicates!r}")
+    for what, ids, length in (("img_ids", img_ids, b), ("txt_ids", txt_ids, n)):
+        if not _vec_ok(ids, torch.int64, length, dev):
+            raise RuntimeError(
+                f"{what} must be a contiguous int64 ({length},) tensor on "
+                f"{dev} (got {getattr(ids, 'dtype', type(ids))} "
+                f"{tuple(getattr(ids, 'shape', ()))} on "
+                f"{getattr(ids, 'device', None)})")
+
+
 def sigmoid_ids(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
                 bias: torch.Tensor, img_ids: torch.Tensor,
                 txt_ids: torch.Tensor, duplicates: str = "positive",
@@ -1218,15 +1256,7 @@ def sigmoid_ids(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
     write; only its elements are touched.  ``t_prime`` and ``bias`` are read
     on the device (no host sync).  No autograd."""
     zi, zt, b, n, d, dev = _pair_block("sigmoid_ids", zimg, ztxt)
-    if duplicates not in _DUPLICATES:
-        raise ValueError(f"unknown duplicates {duplicates!r}")
-    for what, ids, length in (("img_ids", img_ids, b), ("txt_ids", txt_ids, n)):
-        if not _vec_ok(ids, torch.int64, length, dev):
-            raise RuntimeError(
-                f"{what} must be a contiguous int64 ({length},) tensor on "
-                f"{dev} (got {getattr(ids, 'dtype', type(ids))} "
-                f"{tuple(getattr(ids, 'shape', ()))} on "
-                f"{getattr(ids, 'device', None)})")
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
     ldg = n
     if want_g:
         g, ldg = _g_view(g, b, n, dev)
@@ -1245,6 +1275,134 @@ def sigmoid_ids(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
         _DUPLICATES[duplicates]),
         "sigmoid_ids_bf16")
     return partials, g
+
+
+class PairLseIds(NamedTuple):
+    """What :func:`pair_lse_ids` returns; a skipped side is three ``None``."""
+    row_lse: Optional[torch.Tensor]
+    row_pos: Optional[torch.Tensor]
+    row_cnt: Optional[torch.Tensor]
+    col_lse: Optional[torch.Tensor]
+    col_pos: Optional[torch.Tensor]
+    col_cnt: Optional[torch.Tensor]
+
+
+def pair_lse_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                 t_prime: torch.Tensor, img_ids: torch.Tensor,
+                 txt_ids: torch.Tensor, duplicates: str = "positive",
+                 diag_offset: Optional[int] = None, rows: bool = True,
+                 cols: bool = True) -> PairLseIds:
+    """Masked log-sum-exp, positive-logit sum and positive count of every row
+    and every column of the ``(b, n)`` logit grid ``z = exp(t')·zimg @ ztxtᵀ``
+    with sample-ID labels, without materializing the grid →
+    :class:`PairLseIds` of fresh tensors; a side that is switched off is
+    skipped and returned as ``None``.
+
+    Pair classes are those of :func:`sigmoid_ids`: a pair with a negative id
+    on either side is masked; ``duplicates="positive"`` makes a pair positive
+    where the ids are equal; ``"ignore"`` makes ``j == i + diag_offset`` the
+    positive (``None``: none) and masks every other pair with equal ids.  A
+    masked pair is never a positive.  Then ``lse`` (fp32) runs over the pairs
+    that are not masked (``−inf`` where there is none), ``pos`` (fp32) is the
+    sum of ``z`` over the positives and ``cnt`` (int32, exact) their number.
+
+    One MFMA pass leaves per-tile partials in workspaces from the torch
+    allocator (16 bytes per row and column tile), a second kernel folds them
+    in tile order: no atomics, bitwise reproducible.  ``t_prime`` is read on
+    the device (no host sync).  Ids are contiguous int64 ``(b,)`` / ``(n,)``
+    on the embeddings' device and are compared as 64-bit values.  Column
+    chunks (``ztxt[j0:j1]``, ``txt_ids[j0:j1]``, ``diag_offset − j0``)
+    compose in the caller: ``torch.logaddexp`` of the row LSEs, sums of the
+    row ``pos`` and ``cnt``.  No autograd."""
+    zi, zt, b, n, d, dev = _pair_block("pair_lse_ids", zimg, ztxt)
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
+    if not rows and not cols:
+        return PairLseIds(None, None, None, None, None, None)
+    lib = _require_lib()
+    tile = lib.softmax_ids_tile_dim()
+    tp = _prep_scalar(t_prime, dev)
+
+    def side(on, tiles, length):
+        if not on:
+            return None, None, None, None
+        # 16-byte records (max, Σ exp, Σ positive logits, count).
+        return (torch.empty((tiles, length, 4), device=dev,
+                            dtype=torch.int32),
+                torch.empty(length, device=dev, dtype=torch.float32),
+                torch.empty(length, device=dev, dtype=torch.float32),
+                torch.empty(length, device=dev, dtype=torch.int32))
+
+    row_ws, row_lse, row_pos, row_cnt = side(rows, -(-n // tile), b)
+    col_ws, col_lse, col_pos, col_cnt = side(cols, -(-b // tile), n)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.softmax_ids_lse_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(img_ids),
+        _ptr(txt_ids), _ptr(row_ws), _ptr(col_ws), _ptr(row_lse),
+        _ptr(row_pos), _ptr(row_cnt), _ptr(col_lse), _ptr(col_pos),
+        _ptr(col_cnt), b, n, d, _diag_arg(diag_offset),
+        _DUPLICATES[duplicates]), "softmax_ids_lse_bf16")
+    return PairLseIds(row_lse, row_pos, row_cnt, col_lse, col_pos, col_cnt)
+
+
+def _softmax_ids_side(name: str, lse, w, pw, length: int, device):
+    """Validate one side of :func:`softmax_g_ids`: all three vectors or
+    none."""
+    if (lse is None) != (pw is None):
+        raise RuntimeError(
+            f"{name}_lse, {name}_w and {name}_pw must be given together")
+    _softmax_side(name, lse, w, length, device)
+    if pw is not None and not _vec_ok(pw, torch.float32, length, device):
+        raise RuntimeError(
+            f"{name}_pw must be a contiguous fp32 ({length},) tensor on "
+            f"{device} (got {pw.dtype} {tuple(pw.shape)} on {pw.device})")
+    return lse, w, pw
+
+
+def softmax_g_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                  t_prime: torch.Tensor, img_ids: torch.Tensor,
+                  txt_ids: torch.Tensor, duplicates: str,
+                  diag_offset: Optional[int],
+                  row_lse: Optional[torch.Tensor],
+                  row_w: Optional[torch.Tensor],
+                  row_pw: Optional[torch.Tensor],
+                  col_lse: Optional[torch.Tensor],
+                  col_w: Optional[torch.Tensor],
+                  col_pw: Optional[torch.Tensor],
+                  g: Optional[torch.Tensor] = None):
+    """dL/dlogit of the softmax contrastive loss with sample-ID labels over
+    the ``(b, n)`` block → ``(g, gs_partials)``:
+
+    ``g_ij = row_w_i·exp(z_ij − row_lse_i) + col_w_j·exp(z_ij − col_lse_j)
+    − [positive]·(row_pw_i + col_pw_j)``, exactly 0 where the pair is masked
+    (classes as in :func:`pair_lse_ids`), bf16, and one fp32 ``Σ g_ij·s_ij``
+    (``s = z / t``) per 128×128 tile, each reduced in a fixed order
+    (``dt' = t·gs_partials.sum()``).
+
+    The LSE and weight vectors are fp32 ``(b,)`` / ``(n,)``; a side given as
+    three ``None`` adds no term.  ``g`` may be the caller's ``(b, n)`` view
+    with unit column stride — a column band of a wider slab: the view carries
+    the offset and its row stride, so slicing, not pointer arithmetic, bounds
+    the write; only its elements are touched.  No autograd."""
+    zi, zt, b, n, d, dev = _pair_block("softmax_g_ids", zimg, ztxt)
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
+    row_lse, row_w, row_pw = _softmax_ids_side("row", row_lse, row_w, row_pw,
+                                               b, dev)
+    col_lse, col_w, col_pw = _softmax_ids_side("col", col_lse, col_w, col_pw,
+                                               n, dev)
+    g, ldg = _g_view(g, b, n, dev)
+    lib = _require_lib()
+    tile = lib.softmax_ids_tile_dim()
+    tp = _prep_scalar(t_prime, dev)
+    gs = torch.empty(-(-b // tile) * -(-n // tile), device=dev,
+                     dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.softmax_ids_g_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(img_ids),
+        _ptr(txt_ids), _ptr(row_lse), _ptr(row_w), _ptr(row_pw),
+        _ptr(col_lse), _ptr(col_w), _ptr(col_pw), _ptr(g), _ptr(gs), b, n, d,
+        ctypes.c_longlong(ldg), _diag_arg(diag_offset),
+        _DUPLICATES[duplicates]), "softmax_ids_g_bf16")
+    return g, gs
 
 
 class _FusedL2Normalize(torch.autograd.Function):

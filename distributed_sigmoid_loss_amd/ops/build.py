@@ -2,10 +2,11 @@
 
 Compiles ``kernels/siglip_kernels.hip``, ``kernels/wgrad_kernels.hip``,
 ``kernels/rank_kernels.hip``, ``kernels/softmax_kernels.hip``,
-``kernels/topk_kernels.hip`` and ``kernels/idlabel_kernels.hip`` with hipcc into
-``ops/_siglip_hip.so`` (plain C ABI, loaded via ctypes — no torch C++ ABI
-coupling, so a single .so works across torch builds and travels with the
-repo snapshot to GPU boxes).  The last four include ``kernels/pair_tile.h``,
+``kernels/topk_kernels.hip``, ``kernels/idlabel_kernels.hip`` and
+``kernels/softmax_id_kernels.hip`` with hipcc into ``ops/_siglip_hip.so``
+(plain C ABI, loaded via ctypes — no torch C++ ABI coupling, so a single .so
+works across torch builds and travels with the repo snapshot to GPU boxes).
+The last five include ``kernels/pair_tile.h``,
 which sits next to them and needs no include flag; the extension is rebuilt
 when a source or any header under ``kernels/`` is newer than the ``.so``.
 
@@ -26,7 +27,8 @@ _SRCS = [os.path.join(_OPS_DIR, "kernels", "siglip_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "rank_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "softmax_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "topk_kernels.hip"),
-         os.path.join(_OPS_DIR, "kernels", "idlabel_kernels.hip")]
+         os.path.join(_OPS_DIR, "kernels", "idlabel_kernels.hip"),
+         os.path.join(_OPS_DIR, "kernels", "softmax_id_kernels.hip")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

@@ -40,6 +40,8 @@ from typing import Optional
 import torch
 import torch.nn.functional as F
 
+from .. import ops
+
 # With col_chunk=None the GPU backward uses a single g slab whenever its
 # 32-bit store addressing allows (b·n·esz < 2^32) and auto-halves the slab
 # otherwise — e.g. per-GPU b=131072 against n=131072 runs at 8192-column
@@ -122,7 +124,6 @@ def chunk_loss_fwd(zimg, ztxt, t_prime, bias, diag_offset=None,
     if impl == "auto":
         impl = "hip" if zimg.is_cuda else "torch"
     if impl == "hip":
-        from .. import ops
         return ops.siglip_fwd(zimg.contiguous(), ztxt.contiguous(), t_prime,
                               bias, diag_offset, quant=quant, qcache=qcache)
     with torch.no_grad():
@@ -142,7 +143,6 @@ def chunk_loss_bwd(zimg, ztxt, t_prime, bias, diag_offset, grad_output,
     if impl == "auto":
         impl = "hip" if zimg.is_cuda else "torch"
     if impl == "hip":
-        from .. import ops
         return ops.siglip_bwd(zimg.contiguous(), ztxt.contiguous(), t_prime,
                               bias, diag_offset, grad_output, col_chunk,
                               quant=quant, on_dztxt=on_dztxt, qcache=qcache)
@@ -179,7 +179,6 @@ class _FusedSigmoidLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, zimg, ztxt, t_prime, bias, diag_offset, col_chunk,
                 quant, want_grad):
-        from .. import ops
         zimg = zimg.contiguous()
         ztxt = ztxt.contiguous()
         b, n = zimg.shape[0], ztxt.shape[0]
@@ -211,15 +210,12 @@ class _FusedSigmoidLoss(torch.autograd.Function):
             loss = out3[0].clone()
             regime = (out3, g) + ((gt,) if gt is not None else ())
         elif banded:
-            step = ops.banded_col_step(b)
             buf = ops._out_buf(zimg.device)
             slabs = []
-            for j0 in range(0, n, step):
-                j1 = min(j0 + step, n)
+            for j0, j1, diag in ops.col_bands(n, ops.banded_col_step(b),
+                                              diag_offset):
                 g_s = torch.empty((b, j1 - j0), device=zimg.device,
                                   dtype=torch.bfloat16)
-                diag = (None if diag_offset is None
-                        else int(diag_offset) - j0)
                 ops.siglip_fwd_g(zimg, ztxt[j0:j1].contiguous(), t_prime,
                                  bias, diag, quant=quant, g_slab=g_s,
                                  out3=buf)
@@ -243,7 +239,6 @@ class _FusedSigmoidLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        from .. import ops
         saved = ctx.saved_tensors
         inputs = saved[:4]
         regime = saved[4:len(saved) - ctx.n_qc]

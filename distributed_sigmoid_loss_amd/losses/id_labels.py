@@ -39,8 +39,8 @@ tile, never building the logits, in one of two regimes:
   in one pass; the backward is the two gradient GEMMs (``ops.grad_gemms``)
   plus the scalar gradients from the saved partials.
 - *band recompute* — otherwise: the forward runs the loss-only kernel per
-  column chunk; the backward re-runs the kernel per band into one reused
-  slab and feeds the lazy band iterator of ``ops.grad_gemms``.
+  column chunk; the backward re-runs the kernel per band through
+  ``ops.band_grad_gemms``.
 
 Per-tile partials are summed in fp64 on the device; nothing syncs with the
 host.  Elsewhere a differentiable torch composite with the same contract runs
@@ -53,6 +53,8 @@ from typing import Optional
 
 import torch
 import torch.nn.functional as F
+
+from .. import ops
 
 _DUPLICATES = ("positive", "ignore")
 
@@ -111,7 +113,6 @@ class _FusedIdLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, zimg, ztxt, t_prime, bias, img_ids, txt_ids, duplicates,
                 diag_offset, col_chunk, want_grad):
-        from .. import ops
         zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
         b, n = zimg.shape[0], ztxt.shape[0]
         # want_grad comes from the caller (grad mode is off in here).
@@ -128,13 +129,10 @@ class _FusedIdLoss(torch.autograd.Function):
             step = min(n, int(col_chunk) if col_chunk and col_chunk > 0
                        else ops.banded_col_step(b))
             loss = torch.zeros((), device=zimg.device, dtype=torch.float64)
-            for j0 in range(0, n, step):
-                j1 = min(j0 + step, n)
+            for j0, j1, diag_j in ops.col_bands(n, step, diag_offset):
                 partials, _ = ops.sigmoid_ids(
                     zimg, ztxt[j0:j1], t_prime, bias, img_ids,
-                    txt_ids[j0:j1], duplicates,
-                    None if diag_offset is None else int(diag_offset) - j0,
-                    want_g=False)
+                    txt_ids[j0:j1], duplicates, diag_j, want_g=False)
                 # the same reduction as saved-g: one block gives the same bits
                 loss = loss + partials.double().sum(dim=0)[0]
             ctx.save_for_backward(zimg, ztxt, t_prime, bias, img_ids,
@@ -146,43 +144,28 @@ class _FusedIdLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        from .. import ops
         zimg, ztxt, t_prime, bias, img_ids, txt_ids = ctx.saved_tensors[:6]
-        b, n = zimg.shape[0], ztxt.shape[0]
-        dev = zimg.device
-        go = grad_output.detach().reshape(()).to(device=dev,
-                                                 dtype=torch.float32)
-        t = t_prime.detach().reshape(()).to(device=dev,
-                                            dtype=torch.float32).exp()
+        n, dev = ztxt.shape[0], zimg.device
+        go = ops._go_scalar(grad_output, dev)
+        t = ops._prep_scalar(t_prime, dev).exp()
         if ctx.save_g:
             sums, g = ctx.saved_tensors[6:]
             # bf16_scale=True: the products stay bf16 (see ops.grad_gemms).
             dzimg, dztxt = ops.grad_gemms(ops.GBand(g, None, ztxt), zimg, n,
                                           go * t, bf16_scale=True)
         else:
-            step, diag_offset = ctx.step, ctx.diag_offset
             parts = []
 
-            def band(j0, j1, buf):
-                partials, g = ops.sigmoid_ids(
+            def emit(j0, j1, diag_j, g, gt):
+                partials, _ = ops.sigmoid_ids(
                     zimg, ztxt[j0:j1], t_prime, bias, img_ids,
-                    txt_ids[j0:j1], ctx.duplicates,
-                    None if diag_offset is None else int(diag_offset) - j0,
-                    g=buf)
+                    txt_ids[j0:j1], ctx.duplicates, diag_j, g=g)
                 parts.append(partials.double().sum(dim=0))
-                return ops.GBand(g, None, ztxt[j0:j1])
 
-            def bands():
-                # One reused slab: grad_gemms consumes each band before it
-                # asks for the next, so the stream orders kernel after GEMMs.
-                buf = torch.empty((b, step), device=dev,
-                                  dtype=torch.bfloat16)
-                for j0 in range(0, n, step):
-                    j1 = min(j0 + step, n)
-                    yield band(j0, j1, buf if j1 - j0 == step else None)
-
-            dzimg, dztxt = ops.grad_gemms(
-                band(0, n, None) if step >= n else bands(), zimg, n, go * t)
+            # bf16_scale stays False, also when one band covers the block.
+            dzimg, dztxt = ops.band_grad_gemms(
+                zimg, ztxt, ctx.step, emit, go * t,
+                diag_offset=ctx.diag_offset)
             sums = torch.stack(parts).sum(dim=0)
         dt = sums[1] * (go * t).double()
         db = sums[2] * go.double()

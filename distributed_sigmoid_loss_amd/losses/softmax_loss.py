@@ -56,6 +56,7 @@ import torch
 import torch.nn as nn
 import torch.distributed as dist
 
+from .. import ops
 from ..parallel.collectives import all_gather_with_grad
 from .id_labels import _DUPLICATES, _ids_vector, pair_classes
 from .retrieval import (
@@ -124,6 +125,72 @@ def _is_distributed(group) -> bool:
             and dist.is_initialized() and dist.get_world_size(group) > 1)
 
 
+def _fwd_step(col_chunk, n: int) -> int:
+    """Columns per forward pass (and per torch-path backward band)."""
+    return int(col_chunk) if col_chunk and col_chunk > 0 else n
+
+
+def _owner_go(go, b: int, group):
+    """Under a group column j's term is part of the loss of the rank that
+    holds row j − diag_offset, i.e. rank j // b: the ranks' ``grad_output``
+    scalars, gathered, as an ``(n,)`` vector."""
+    go_all = torch.empty(dist.get_world_size(group), device=go.device,
+                         dtype=go.dtype)
+    dist.all_gather_into_tensor(go_all, go.reshape(1), group=group)
+    return go_all.repeat_interleave(b)
+
+
+def _backward(hip, zimg, ztxt, t_prime, t, col_chunk, diag_offset, g_band,
+              gs_parts, n_inputs):
+    """What the two Functions' backwards share.  ``g_band(j0, j1, diag_j, g,
+    gt)`` returns dL/dlogit of columns ``j0:j1`` — written into ``g`` where
+    one is handed (the hip path) — and appends the band's ``Σ g·s`` partials
+    to ``gs_parts``.  Returns the ``n_inputs`` gradients: dzimg, dztxt, dt'
+    and ``None`` for the rest."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    if hip:
+        # The upstream gradient lives in the weights: the scale is t alone.
+        dzimg, dztxt = ops.band_grad_gemms(
+            zimg, ztxt, ops.g_band_step(b, n, col_chunk), g_band, t,
+            diag_offset=diag_offset)
+    else:
+        cdt = t.dtype
+        zi = zimg.to(cdt)
+        dzimg = torch.zeros((b, zimg.shape[1]), device=t.device, dtype=cdt)
+        dztxt = torch.empty((n, zimg.shape[1]), device=t.device, dtype=cdt)
+        for j0, j1, diag_j in ops.col_bands(n, _fwd_step(col_chunk, n),
+                                            diag_offset):
+            g = g_band(j0, j1, diag_j, None, None)
+            dzimg += g @ ztxt[j0:j1].to(cdt)
+            dztxt[j0:j1] = g.T @ zi
+        dzimg, dztxt = (dzimg * t).to(zimg.dtype), (dztxt * t).to(ztxt.dtype)
+    dt = t.double() * torch.cat(gs_parts).double().sum()
+    return (dzimg, dztxt,
+            dt.to(device=t_prime.device,
+                  dtype=t_prime.dtype).reshape(t_prime.shape)
+            ) + (None,) * (n_inputs - 3)
+
+
+def _check_block(zimg, ztxt, impl: str, group, hip_auto: bool,
+                 duplicates: str = "positive"):
+    """What the public functions check alike → ``(impl, group, world,
+    rank)``: the shapes, ``duplicates``, ``impl`` resolved (``auto`` is
+    ``hip`` given ``hip_auto``), ``group`` as ``None`` unless it spans several
+    ranks."""
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise ValueError(
+            f"shape mismatch: zimg {tuple(zimg.shape)} ztxt {tuple(ztxt.shape)}")
+    if duplicates not in _DUPLICATES:
+        raise ValueError(f"unknown duplicates {duplicates!r}")
+    if impl == "auto":
+        impl = "hip" if hip_auto else "torch"
+    if impl not in ("hip", "torch"):
+        raise ValueError(f"unknown impl {impl!r}")
+    if not _is_distributed(group):
+        return impl, None, 1, 0
+    return impl, group, dist.get_world_size(group), dist.get_rank(group)
+
+
 class _SoftmaxLoss(torch.autograd.Function):
     """Both implementations: ``hip`` runs the fused kernels and the library
     gradient GEMMs, ``torch`` the composites above; the chunking, the
@@ -133,17 +200,12 @@ class _SoftmaxLoss(torch.autograd.Function):
     def forward(ctx, zimg, ztxt, t_prime, diag_offset, col_chunk, impl,
                 group):
         hip = impl == "hip"
-        if hip:
-            from .. import ops
-            lse_fn = ops.pair_lse
-        else:
-            lse_fn = _torch_pair_lse
+        lse_fn = ops.pair_lse if hip else _torch_pair_lse
         zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
         b, n = zimg.shape[0], ztxt.shape[0]
-        step = int(col_chunk) if col_chunk and col_chunk > 0 else n
         row_lse, col_parts = None, []
-        for j0 in range(0, n, step):
-            rl, cl = lse_fn(zimg, ztxt[j0:min(j0 + step, n)], t_prime)
+        for j0, j1, _ in ops.col_bands(n, _fwd_step(col_chunk, n)):
+            rl, cl = lse_fn(zimg, ztxt[j0:j1], t_prime)
             row_lse = rl if row_lse is None else torch.logaddexp(row_lse, rl)
             col_parts.append(cl)
         col_lse = col_parts[0] if len(col_parts) == 1 else torch.cat(col_parts)
@@ -168,74 +230,30 @@ class _SoftmaxLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         zimg, ztxt, t_prime, row_lse, col_lse = ctx.saved_tensors
-        diag_offset, col_chunk = ctx.diag_offset, ctx.col_chunk
         b, n = zimg.shape[0], ztxt.shape[0]
         dev, cdt = zimg.device, row_lse.dtype
-        go = grad_output.detach().reshape(()).to(device=dev, dtype=cdt)
-        rows, cols = _positive_rows(b, n, diag_offset, dev)
+        go = ops._go_scalar(grad_output, dev, cdt)
+        rows, cols = _positive_rows(b, n, ctx.diag_offset, dev)
         row_w = torch.zeros(b, device=dev, dtype=cdt)
         row_w[rows] = go
         if ctx.group is not None:
-            # Column j's LSE term is part of the loss of the rank that holds
-            # row j − diag_offset, i.e. rank j // b.
-            go_all = torch.empty(dist.get_world_size(ctx.group), device=dev,
-                                 dtype=cdt)
-            dist.all_gather_into_tensor(go_all, go.reshape(1),
-                                        group=ctx.group)
-            col_w = go_all.repeat_interleave(b)
+            col_w = _owner_go(go, b, ctx.group)
         else:
             col_w = torch.zeros(n, device=dev, dtype=cdt)
             col_w[cols] = go
         t = t_prime.detach().to(device=dev, dtype=cdt).exp()
+        g_fn = ops.softmax_g if ctx.hip else _torch_softmax_g
         gs_parts = []
 
-        if ctx.hip:
-            from .. import ops
-            whole = col_chunk is None and b * n * 2 < 2 ** 32
-            step = n if whole else (int(col_chunk) if col_chunk
-                                    else ops.banded_col_step(b))
+        def g_band(j0, j1, diag_j, g, gt):
+            g, gs = g_fn(zimg, ztxt[j0:j1], t_prime, row_lse, row_w,
+                         col_lse[j0:j1].contiguous(),
+                         col_w[j0:j1].contiguous(), diag_j, g=g)
+            gs_parts.append(gs)
+            return g
 
-            def band(j0, j1, buf):
-                g, gs = ops.softmax_g(
-                    zimg, ztxt[j0:j1], t_prime, row_lse, row_w,
-                    col_lse[j0:j1].contiguous(), col_w[j0:j1].contiguous(),
-                    None if diag_offset is None else int(diag_offset) - j0,
-                    g=buf)
-                gs_parts.append(gs)
-                return ops.GBand(g, None, ztxt[j0:j1])
-
-            def bands():
-                # One reused slab: grad_gemms consumes each band before it
-                # asks for the next, so the stream orders kernel after GEMMs.
-                buf = torch.empty((b, step), device=dev,
-                                  dtype=torch.bfloat16)
-                for j0 in range(0, n, step):
-                    j1 = min(j0 + step, n)
-                    yield band(j0, j1, buf if j1 - j0 == step else None)
-
-            dzimg, dztxt = ops.grad_gemms(
-                band(0, n, None) if step >= n else bands(), zimg, n, t)
-        else:
-            step = int(col_chunk) if col_chunk and col_chunk > 0 else n
-            zi = zimg.to(cdt)
-            dzimg = torch.zeros((b, zimg.shape[1]), device=dev, dtype=cdt)
-            dztxt = torch.empty((n, zimg.shape[1]), device=dev, dtype=cdt)
-            for j0 in range(0, n, step):
-                j1 = min(j0 + step, n)
-                g, gs = _torch_softmax_g(
-                    zimg, ztxt[j0:j1], t_prime, row_lse, row_w,
-                    col_lse[j0:j1], col_w[j0:j1],
-                    None if diag_offset is None else int(diag_offset) - j0)
-                gs_parts.append(gs)
-                dzimg += g @ ztxt[j0:j1].to(cdt)
-                dztxt[j0:j1] = g.T @ zi
-            dzimg, dztxt = (dzimg * t).to(zimg.dtype), (dztxt * t).to(
-                ztxt.dtype)
-        dt = t.double() * torch.cat(gs_parts).double().sum()
-        return (dzimg, dztxt,
-                dt.to(device=t_prime.device,
-                      dtype=t_prime.dtype).reshape(t_prime.shape),
-                None, None, None, None)
+        return _backward(ctx.hip, zimg, ztxt, t_prime, t, ctx.col_chunk,
+                         ctx.diag_offset, g_band, gs_parts, 7)
 
 
 def softmax_contrastive_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
@@ -265,23 +283,15 @@ def softmax_contrastive_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
 
     Returns a 0-d tensor; the caller normalises.
     """
-    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+    impl, group, world, rank = _check_block(zimg, ztxt, impl, group,
+                                            zimg.is_cuda)
+    b = zimg.shape[0]
+    if group is not None and (ztxt.shape[0] != world * b
+                              or diag_offset != rank * b):
         raise ValueError(
-            f"shape mismatch: zimg {tuple(zimg.shape)} ztxt {tuple(ztxt.shape)}")
-    if impl == "auto":
-        impl = "hip" if zimg.is_cuda else "torch"
-    if impl not in ("hip", "torch"):
-        raise ValueError(f"unknown impl {impl!r}")
-    if not _is_distributed(group):
-        group = None
-    else:
-        world, rank = dist.get_world_size(group), dist.get_rank(group)
-        b = zimg.shape[0]
-        if ztxt.shape[0] != world * b or diag_offset != rank * b:
-            raise ValueError(
-                f"the distributed form needs n == W·b and diag_offset == "
-                f"rank·b (got b={b}, n={ztxt.shape[0]}, W={world}, "
-                f"rank={rank}, diag_offset={diag_offset})")
+            f"the distributed form needs n == W·b and diag_offset == "
+            f"rank·b (got b={b}, n={ztxt.shape[0]}, W={world}, "
+            f"rank={rank}, diag_offset={diag_offset})")
     return _SoftmaxLoss.apply(zimg, ztxt, t_prime, diag_offset, col_chunk,
                               impl, group)
 
@@ -404,22 +414,16 @@ class _SoftmaxIdLoss(torch.autograd.Function):
     def forward(ctx, zimg, ztxt, t_prime, img_ids, txt_ids, duplicates,
                 diag_offset, col_chunk, impl, group):
         hip = impl == "hip"
-        if hip:
-            from .. import ops
-            lse_fn = ops.pair_lse_ids
-        else:
-            lse_fn = _torch_pair_lse_ids
+        lse_fn = ops.pair_lse_ids if hip else _torch_pair_lse_ids
         zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
         b, n = zimg.shape[0], ztxt.shape[0]
-        step = int(col_chunk) if col_chunk and col_chunk > 0 else n
         row_lse = row_pos = row_cnt = None
         col_parts = []
-        for j0 in range(0, n, step):
-            j1 = min(j0 + step, n)
+        for j0, j1, diag_j in ops.col_bands(n, _fwd_step(col_chunk, n),
+                                            diag_offset):
             rl, rp, rc, cl, cp, cc = lse_fn(
                 zimg, ztxt[j0:j1], t_prime, img_ids, txt_ids[j0:j1],
-                duplicates,
-                None if diag_offset is None else int(diag_offset) - j0)
+                duplicates, diag_j)
             if row_lse is None:
                 row_lse, row_pos, row_cnt = rl, rp, rc
             else:
@@ -465,72 +469,27 @@ class _SoftmaxIdLoss(torch.autograd.Function):
     def backward(ctx, grad_output):
         (zimg, ztxt, t_prime, img_ids, txt_ids, row_lse, row_cnt, col_lse,
          col_cnt) = ctx.saved_tensors
-        duplicates, diag_offset = ctx.duplicates, ctx.diag_offset
-        col_chunk = ctx.col_chunk
-        b, n = zimg.shape[0], ztxt.shape[0]
+        b = zimg.shape[0]
         dev, cdt = zimg.device, row_lse.dtype
-        go = grad_output.detach().reshape(()).to(device=dev, dtype=cdt)
-        col_go = go
-        if ctx.group is not None:
-            # Column j's term is part of the loss of rank j // b.
-            go_all = torch.empty(dist.get_world_size(ctx.group), device=dev,
-                                 dtype=cdt)
-            dist.all_gather_into_tensor(go_all, go.reshape(1),
-                                        group=ctx.group)
-            col_go = go_all.repeat_interleave(b)
+        go = ops._go_scalar(grad_output, dev, cdt)
+        col_go = go if ctx.group is None else _owner_go(go, b, ctx.group)
         row_w, row_pw = _id_weights(go, row_cnt, cdt)
         col_w, col_pw = _id_weights(col_go, col_cnt, cdt)
         t = t_prime.detach().to(device=dev, dtype=cdt).exp()
+        g_fn = ops.softmax_g_ids if ctx.hip else _torch_softmax_g_ids
         gs_parts = []
 
-        def g_of(fn, j0, j1, **kw):
-            g, gs = fn(
+        def g_band(j0, j1, diag_j, g, gt):
+            g, gs = g_fn(
                 zimg, ztxt[j0:j1], t_prime, img_ids, txt_ids[j0:j1],
-                duplicates,
-                None if diag_offset is None else int(diag_offset) - j0,
-                row_lse, row_w, row_pw, col_lse[j0:j1].contiguous(),
-                col_w[j0:j1].contiguous(), col_pw[j0:j1].contiguous(), **kw)
+                ctx.duplicates, diag_j, row_lse, row_w, row_pw,
+                col_lse[j0:j1].contiguous(), col_w[j0:j1].contiguous(),
+                col_pw[j0:j1].contiguous(), g=g)
             gs_parts.append(gs)
             return g
 
-        if ctx.hip:
-            from .. import ops
-            whole = col_chunk is None and b * n * 2 < 2 ** 32
-            step = n if whole else (int(col_chunk) if col_chunk
-                                    else ops.banded_col_step(b))
-
-            def band(j0, j1, buf):
-                return ops.GBand(g_of(ops.softmax_g_ids, j0, j1, g=buf),
-                                 None, ztxt[j0:j1])
-
-            def bands():
-                # One reused slab: grad_gemms consumes each band before it
-                # asks for the next, so the stream orders kernel after GEMMs.
-                buf = torch.empty((b, step), device=dev,
-                                  dtype=torch.bfloat16)
-                for j0 in range(0, n, step):
-                    j1 = min(j0 + step, n)
-                    yield band(j0, j1, buf if j1 - j0 == step else None)
-
-            dzimg, dztxt = ops.grad_gemms(
-                band(0, n, None) if step >= n else bands(), zimg, n, t)
-        else:
-            step = int(col_chunk) if col_chunk and col_chunk > 0 else n
-            zi = zimg.to(cdt)
-            dzimg = torch.zeros((b, zimg.shape[1]), device=dev, dtype=cdt)
-            dztxt = torch.empty((n, zimg.shape[1]), device=dev, dtype=cdt)
-            for j0 in range(0, n, step):
-                j1 = min(j0 + step, n)
-                g = g_of(_torch_softmax_g_ids, j0, j1)
-                dzimg += g @ ztxt[j0:j1].to(cdt)
-                dztxt[j0:j1] = g.T @ zi
-            dzimg, dztxt = (dzimg * t).to(zimg.dtype), (dztxt * t).to(
-                ztxt.dtype)
-        dt = t.double() * torch.cat(gs_parts).double().sum()
-        return (dzimg, dztxt,
-                dt.to(device=t_prime.device,
-                      dtype=t_prime.dtype).reshape(t_prime.shape),
-                None, None, None, None, None, None, None)
+        return _backward(ctx.hip, zimg, ztxt, t_prime, t, ctx.col_chunk,
+                         ctx.diag_offset, g_band, gs_parts, 10)
 
 
 def softmax_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
@@ -579,32 +538,23 @@ def softmax_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
 
     Returns a 0-d tensor; the caller normalises.
     """
-    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
-        raise ValueError(
-            f"shape mismatch: zimg {tuple(zimg.shape)} ztxt {tuple(ztxt.shape)}")
-    if duplicates not in _DUPLICATES:
-        raise ValueError(f"unknown duplicates {duplicates!r}")
-    if impl == "auto":
-        impl = ("hip" if zimg.is_cuda and zimg.dtype == torch.bfloat16
-                and ztxt.dtype == torch.bfloat16 else "torch")
-    if impl not in ("hip", "torch"):
-        raise ValueError(f"unknown impl {impl!r}")
-    img_ids = _ids_vector("img_ids", img_ids, zimg.shape[0], zimg.device)
+    impl, group, world, rank = _check_block(
+        zimg, ztxt, impl, group,
+        zimg.is_cuda and zimg.dtype == torch.bfloat16
+        and ztxt.dtype == torch.bfloat16, duplicates)
+    b = zimg.shape[0]
+    img_ids = _ids_vector("img_ids", img_ids, b, zimg.device)
     txt_ids = _ids_vector("txt_ids", txt_ids, ztxt.shape[0], zimg.device)
     if duplicates != "ignore":
         diag_offset = None
-    if not _is_distributed(group):
-        group = None
-    else:
-        world, rank = dist.get_world_size(group), dist.get_rank(group)
-        b = zimg.shape[0]
-        if ztxt.shape[0] != world * b or (duplicates == "ignore"
-                                          and diag_offset != rank * b):
-            raise ValueError(
-                f"the distributed form needs n == W·b and, with "
-                f"duplicates='ignore', diag_offset == rank·b (got b={b}, "
-                f"n={ztxt.shape[0]}, W={world}, rank={rank}, "
-                f"diag_offset={diag_offset})")
+    if group is not None and (ztxt.shape[0] != world * b
+                              or (duplicates == "ignore"
+                                  and diag_offset != rank * b)):
+        raise ValueError(
+            f"the distributed form needs n == W·b and, with "
+            f"duplicates='ignore', diag_offset == rank·b (got b={b}, "
+            f"n={ztxt.shape[0]}, W={world}, rank={rank}, "
+            f"diag_offset={diag_offset})")
     return _SoftmaxIdLoss.apply(zimg, ztxt, t_prime, img_ids, txt_ids,
                                 duplicates, diag_offset, col_chunk, impl,
                                 group)
@@ -644,28 +594,34 @@ class DistributedSoftmaxLoss(nn.Module):
         self.impl = impl
         self.max_logit_scale = max_logit_scale
 
-    def _forward_ids(self, image_embeddings, text_embeddings, group,
-                     image_ids, text_ids, duplicates):
+    def _gather_text(self, text_embeddings, group):
+        """What both label forms start with → ``(world, rank, t', all text
+        shards, the group to reduce over or None at one rank)``."""
         world, rank = 1, 0
         if dist.is_available() and dist.is_initialized():
             world, rank = dist.get_world_size(group), dist.get_rank(group)
-        b_txt = text_embeddings.shape[0]
         t_prime = self.t_prime.clamp(max=math.log(self.max_logit_scale))
+        all_txt = all_gather_with_grad(text_embeddings, group=group)
+        if world > 1 and group is None:
+            group = dist.group.WORLD
+        return world, rank, t_prime, all_txt, group if world > 1 else None
+
+    def _forward_ids(self, image_embeddings, text_embeddings, group,
+                     image_ids, text_ids, duplicates):
+        b_txt = text_embeddings.shape[0]
         text_ids = _ids_vector("text_ids", text_ids, b_txt,
                                text_embeddings.device)
-        all_txt = all_gather_with_grad(text_embeddings, group=group)
+        world, rank, t_prime, all_txt, group = self._gather_text(
+            text_embeddings, group)
         all_ids = text_ids
-        if world > 1:
-            if group is None:
-                group = dist.group.WORLD
+        if group is not None:
             all_ids = torch.empty(world * b_txt, device=text_ids.device,
                                   dtype=torch.int64)
             dist.all_gather_into_tensor(all_ids, text_ids, group=group)
         total = softmax_contrastive_loss_ids(
             image_embeddings, all_txt, t_prime, image_ids, all_ids,
             duplicates=duplicates, diag_offset=rank * b_txt,
-            col_chunk=self.col_chunk, impl=self.impl,
-            group=group if world > 1 else None)
+            col_chunk=self.col_chunk, impl=self.impl, group=group)
         return total / (2 * self.gpu_batch_size)
 
     def forward(self, image_embeddings: torch.Tensor,
@@ -679,16 +635,10 @@ class DistributedSoftmaxLoss(nn.Module):
         if image_ids is not None:
             return self._forward_ids(image_embeddings, text_embeddings,
                                      group, image_ids, text_ids, duplicates)
-        world, rank = 1, 0
-        if dist.is_available() and dist.is_initialized():
-            world, rank = dist.get_world_size(group), dist.get_rank(group)
-        t_prime = self.t_prime.clamp(max=math.log(self.max_logit_scale))
-        all_txt = all_gather_with_grad(text_embeddings, group=group)
-        if world > 1 and group is None:
-            group = dist.group.WORLD
+        _, rank, t_prime, all_txt, group = self._gather_text(
+            text_embeddings, group)
         total = softmax_contrastive_loss(
             image_embeddings, all_txt, t_prime,
             diag_offset=rank * text_embeddings.shape[0],
-            col_chunk=self.col_chunk, impl=self.impl,
-            group=group if world > 1 else None)
+            col_chunk=self.col_chunk, impl=self.impl, group=group)
         return total / (2 * self.gpu_batch_size)

@@ -52,7 +52,9 @@ Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
 backward regime (recompute, saved-g, banded saved-g, the fp8 ring) runs its
 two gradient GEMMs through :func:`grad_gemms` and its scalar gradients
-through :func:`scalar_grads`; a quantization made once per step travels as a
+through :func:`scalar_grads`; every column-banded recompute backward (the
+sigmoid, sample-ID and softmax losses) hands its g-emitting kernel to
+:func:`band_grad_gemms`; a quantization made once per step travels as a
 :class:`QuantCache`.
 
 These are *loud* paths: calling them on a GPU without the built extension
@@ -157,6 +159,49 @@ def load_tuned_gemms() -> bool:
     return True
 
 
+_P, _I, _L = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+
+# Every export of the extension, name → argument types; all return int.
+_EXPORTS = {
+    "siglip_ext_abi": [],
+    # (stream, mode, eb, eb_g, 11 pointers, b, n, d, ldg, diag, flags)
+    "siglip_tile": [_P] + [_I] * 3 + [_P] * 11 + [_I] * 6,
+    "l2norm_fwd_bf16": [_P] * 4 + [_I] * 2 + [ctypes.c_float],
+    "l2norm_bwd_bf16": [_P] * 5 + [_I] * 2,
+    "quant_fp8_bf16": [_P] * 5 + [_L],
+    "quant_fp8_rowwise_bf16": [_P] * 5 + [_I] * 2,
+    "linear_wgrad_plan": [_I] * 4,
+    # (stream, a, x, ws, dw, K, M, N, lda, ldx, slices)
+    "linear_wgrad_bf16": [_P] * 5 + [_I] * 3 + [_L] * 2 + [_I],
+    "scale_bf16_inplace": [_P] * 3 + [_L],
+    # (stream, zimg, ztxt, row_thr, col_thr, row_cnt, col_cnt, b, n, d, diag)
+    "pair_rank_counts_bf16": [_P] * 7 + [_I] * 4,
+    "softmax_tile_dim": [],
+    # (stream, zimg, ztxt, t', row_ws, col_ws, row_lse, col_lse, b, n, d)
+    "softmax_lse_bf16": [_P] * 8 + [_I] * 3,
+    # (stream, zimg, ztxt, t', row_lse, row_w, col_lse, col_w, g, gs_ws,
+    #  b, n, d, ldg, diag)
+    "softmax_g_bf16": [_P] * 10 + [_I] * 3 + [_L] + [_I],
+    "pair_topk_max_k": [],
+    "pair_topk_tile_dim": [],
+    "pair_topk_capacity": [_I],
+    # (stream, zimg, ztxt, ws_s, ws_c, out_s, out_c, b, n, d, diag, k,
+    #  n_splits)
+    "pair_topk_bf16": [_P] * 7 + [_I] * 6,
+    "sigmoid_ids_tile_dim": [],
+    # (stream, zimg, ztxt, t', bias, img_ids, txt_ids, g, ws, b, n, d, ldg,
+    #  diag, mode)
+    "sigmoid_ids_bf16": [_P] * 9 + [_I] * 3 + [_L] + [_I] * 2,
+    "softmax_ids_tile_dim": [],
+    # (stream, zimg, ztxt, t', img_ids, txt_ids, row_ws, col_ws, row_lse,
+    #  row_pos, row_cnt, col_lse, col_pos, col_cnt, b, n, d, diag, mode)
+    "softmax_ids_lse_bf16": [_P] * 14 + [_I] * 5,
+    # (stream, zimg, ztxt, t', img_ids, txt_ids, row_lse, row_w, row_pw,
+    #  col_lse, col_w, col_pw, g, gs_ws, b, n, d, ldg, diag, mode)
+    "softmax_ids_g_bf16": [_P] * 14 + [_I] * 3 + [_L] + [_I] * 2,
+}
+
+
 def _load():
     global _lib, _lib_err
     if _lib is not None or _lib_err is not None:
@@ -171,104 +216,20 @@ def _load():
     except OSError as e:  # pragma: no cover
         _lib_err = f"failed to load {SO_PATH}: {e}"
         return None
-    lib.siglip_ext_abi.restype = ctypes.c_int
-    if lib.siglip_ext_abi() != 13:
-        _lib_err = (f"stale HIP extension at {SO_PATH} "
-                    f"(ABI {lib.siglip_ext_abi()}, need 13); rebuild with: "
-                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
+    # One staleness rule: a missing export, or another ABI number.
+    why = next((f"no {name}" for name in _EXPORTS if not hasattr(lib, name)),
+               None)
+    if why is None:
+        for name, argtypes in _EXPORTS.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = _I, argtypes
+        if lib.siglip_ext_abi() != 13:
+            why = f"ABI {lib.siglip_ext_abi()}, need 13"
+    if why is not None:
+        _lib_err = (f"stale HIP extension at {SO_PATH} ({why}); rebuild "
+                    "with: python -m distributed_sigmoid_loss_amd.ops.build "
+                    "--force")
         return None
-    # (stream, mode, eb, eb_g, 11 pointers, b, n, d, ldg, diag, flags)
-    lib.siglip_tile.restype = ctypes.c_int
-    lib.siglip_tile.argtypes = ([ctypes.c_void_p] + [ctypes.c_int] * 3
-                                + [ctypes.c_void_p] * 11
-                                + [ctypes.c_int] * 6)
-    lib.l2norm_fwd_bf16.restype = ctypes.c_int
-    lib.l2norm_fwd_bf16.argtypes = (
-        [ctypes.c_void_p] * 4 + [ctypes.c_int] * 2 + [ctypes.c_float])
-    lib.l2norm_bwd_bf16.restype = ctypes.c_int
-    lib.l2norm_bwd_bf16.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2
-    lib.quant_fp8_bf16.restype = ctypes.c_int
-    lib.quant_fp8_bf16.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_longlong]
-    lib.quant_fp8_rowwise_bf16.restype = ctypes.c_int
-    lib.quant_fp8_rowwise_bf16.argtypes = (
-        [ctypes.c_void_p] * 5 + [ctypes.c_int] * 2)
-    lib.linear_wgrad_plan.restype = ctypes.c_int
-    lib.linear_wgrad_plan.argtypes = [ctypes.c_int] * 4
-    # (stream, a, x, ws, dw, K, M, N, lda, ldx, slices)
-    lib.linear_wgrad_bf16.restype = ctypes.c_int
-    lib.linear_wgrad_bf16.argtypes = (
-        [ctypes.c_void_p] * 5 + [ctypes.c_int] * 3
-        + [ctypes.c_longlong] * 2 + [ctypes.c_int])
-    lib.scale_bf16_inplace.restype = ctypes.c_int
-    lib.scale_bf16_inplace.argtypes = (
-        [ctypes.c_void_p] * 3 + [ctypes.c_longlong])
-    # (stream, zimg, ztxt, row_thr, col_thr, row_cnt, col_cnt, b, n, d, diag)
-    lib.pair_rank_counts_bf16.restype = ctypes.c_int
-    lib.pair_rank_counts_bf16.argtypes = (
-        [ctypes.c_void_p] * 7 + [ctypes.c_int] * 4)
-    if not hasattr(lib, "softmax_lse_bf16"):
-        _lib_err = (f"stale HIP extension at {SO_PATH} (no softmax kernels); "
-                    "rebuild with: "
-                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
-        return None
-    lib.softmax_tile_dim.restype = ctypes.c_int
-    lib.softmax_tile_dim.argtypes = []
-    # (stream, zimg, ztxt, t', row_ws, col_ws, row_lse, col_lse, b, n, d)
-    lib.softmax_lse_bf16.restype = ctypes.c_int
-    lib.softmax_lse_bf16.argtypes = (
-        [ctypes.c_void_p] * 8 + [ctypes.c_int] * 3)
-    # (stream, zimg, ztxt, t', row_lse, row_w, col_lse, col_w, g, gs_ws,
-    #  b, n, d, ldg, diag)
-    lib.softmax_g_bf16.restype = ctypes.c_int
-    lib.softmax_g_bf16.argtypes = (
-        [ctypes.c_void_p] * 10 + [ctypes.c_int] * 3 + [ctypes.c_longlong]
-        + [ctypes.c_int])
-    if not hasattr(lib, "pair_topk_bf16"):
-        _lib_err = (f"stale HIP extension at {SO_PATH} (no top-k kernels); "
-                    "rebuild with: "
-                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
-        return None
-    for fn in (lib.pair_topk_max_k, lib.pair_topk_tile_dim):
-        fn.restype = ctypes.c_int
-        fn.argtypes = []
-    lib.pair_topk_capacity.restype = ctypes.c_int
-    lib.pair_topk_capacity.argtypes = [ctypes.c_int]
-    # (stream, zimg, ztxt, ws_s, ws_c, out_s, out_c, b, n, d, diag, k,
-    #  n_splits)
-    lib.pair_topk_bf16.restype = ctypes.c_int
-    lib.pair_topk_bf16.argtypes = (
-        [ctypes.c_void_p] * 7 + [ctypes.c_int] * 6)
-    if not hasattr(lib, "sigmoid_ids_bf16"):
-        _lib_err = (f"stale HIP extension at {SO_PATH} (no sample-ID "
-                    "kernels); rebuild with: "
-                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
-        return None
-    lib.sigmoid_ids_tile_dim.restype = ctypes.c_int
-    lib.sigmoid_ids_tile_dim.argtypes = []
-    # (stream, zimg, ztxt, t', bias, img_ids, txt_ids, g, ws, b, n, d, ldg,
-    #  diag, mode)
-    lib.sigmoid_ids_bf16.restype = ctypes.c_int
-    lib.sigmoid_ids_bf16.argtypes = (
-        [ctypes.c_void_p] * 9 + [ctypes.c_int] * 3 + [ctypes.c_longlong]
-        + [ctypes.c_int] * 2)
-    if not hasattr(lib, "softmax_ids_lse_bf16"):
-        _lib_err = (f"stale HIP extension at {SO_PATH} (no softmax sample-ID "
-                    "kernels); rebuild with: "
-                    "python -m distributed_sigmoid_loss_amd.ops.build --force")
-        return None
-    lib.softmax_ids_tile_dim.restype = ctypes.c_int
-    lib.softmax_ids_tile_dim.argtypes = []
-    # (stream, zimg, ztxt, t', img_ids, txt_ids, row_ws, col_ws, row_lse,
-    #  row_pos, row_cnt, col_lse, col_pos, col_cnt, b, n, d, diag, mode)
-    lib.softmax_ids_lse_bf16.restype = ctypes.c_int
-    lib.softmax_ids_lse_bf16.argtypes = (
-        [ctypes.c_void_p] * 14 + [ctypes.c_int] * 5)
-    # (stream, zimg, ztxt, t', img_ids, txt_ids, row_lse, row_w, row_pw,
-    #  col_lse, col_w, col_pw, g, gs_ws, b, n, d, ldg, diag, mode)
-    lib.softmax_ids_g_bf16.restype = ctypes.c_int
-    lib.softmax_ids_g_bf16.argtypes = (
-        [ctypes.c_void_p] * 14 + [ctypes.c_int] * 3 + [ctypes.c_longlong]
-        + [ctypes.c_int] * 2)
     _lib = lib
     return _lib
 
@@ -292,6 +253,13 @@ def _check(rc: int, what: str):
 def _prep_scalar(p: torch.Tensor, device) -> torch.Tensor:
     t = p.detach().reshape(()).to(device=device, dtype=torch.float32)
     return t.contiguous()
+
+
+def _go_scalar(grad_output: torch.Tensor, device,
+               dtype=torch.float32) -> torch.Tensor:
+    """A backward's upstream gradient as a 0-d ``dtype`` scalar on
+    ``device``."""
+    return grad_output.detach().reshape(()).to(device=device, dtype=dtype)
 
 
 def _validate(zimg: torch.Tensor, ztxt: torch.Tensor, quant: str):
@@ -574,31 +542,17 @@ def siglip_bwd(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
             f"batch {b} too large for the 32-bit g-slab addressing even at "
             f"the 256-column slab floor; shard the batch")
 
-    def slabs(c):
-        return (torch.empty((b, c), device=dev, dtype=g_dtype),
-                torch.empty((c, b), device=dev, dtype=g_dtype)
-                if fp8g else None)
-
-    def band(j0, j1, g, gt):
+    def emit(j0, j1, diag_j, g, gt):
         _launch_tile(1, quant, zi_k, zt_k[j0:j1], tp_k, bp, scal, g=g, gt=gt,
-                     diag_offset=(None if diag_offset is None
-                                  else int(diag_offset) - j0))
-        return GBand(g, gt, ztxt[j0:j1], qc and qc.text_rows(j0, j1))
+                     diag_offset=diag_j)
 
-    def chunks():
-        # One reused workspace pair: grad_gemms consumes each band before
-        # asking for the next, so the stream orders kernel after GEMMs.
-        bufs = slabs(step)
-        for j0 in range(0, n, step):
-            j1 = min(j0 + step, n)
-            yield band(j0, j1, *(bufs if j1 - j0 == step else slabs(j1 - j0)))
-
-    go = grad_output.detach().reshape(()).to(device=dev, dtype=torch.float32)
-    # Single slab: no fp32 accumulation round trips.  bf16_scale=False: the
-    # recompute path multiplies by the fp32 scale, then casts.
-    dzimg, dztxt = grad_gemms(
-        band(0, n, *slabs(n)) if step >= n else chunks(), zimg, n,
-        go * tp.exp(), on_dztxt=on_dztxt, bf16_scale=False)
+    go = _go_scalar(grad_output, dev)
+    # bf16_scale=False: the recompute path multiplies by the fp32 scale,
+    # then casts.
+    dzimg, dztxt = band_grad_gemms(
+        zimg, ztxt, step, emit, go * tp.exp(), diag_offset=diag_offset,
+        g_dtype=g_dtype, with_gt=fp8g, qc=qc, on_dztxt=on_dztxt,
+        bf16_scale=False)
     # t_eff ≡ t for bf16/mixed; for fp8 the kernel's dot is of quantized rows.
     dt_prime, dbias = scalar_grads(reduce_out3(scal), go, tp_k.exp(),
                                    t_prime, bias)
@@ -665,6 +619,25 @@ def banded_col_step(b: int, esz: int = 2) -> int:
         return max(256, int(env))
     step = (2 ** 32 - 1) // (b * esz)
     return max(256, (step // 256) * 256)
+
+
+def g_band_step(b: int, n: int, col_chunk: Optional[int]) -> int:
+    """Columns per bf16 g band of a recompute backward: ``n`` — the whole
+    block as one slab — without a ``col_chunk`` while that slab stays under
+    the kernels' 32-bit addressing, else ``col_chunk`` or
+    :func:`banded_col_step`."""
+    if col_chunk is None and b * n * 2 < 2 ** 32:
+        return n
+    return int(col_chunk) if col_chunk else banded_col_step(b)
+
+
+def col_bands(n: int, step: int, diag_offset: Optional[int] = None):
+    """``(j0, j1, diag_j)`` of the column bands ``j0:j1`` of ``n`` columns,
+    ``step`` wide but for a ragged last one; ``diag_j`` is ``diag_offset`` as
+    the band's own columns see it (``None`` stays ``None``)."""
+    for j0 in range(0, n, step):
+        yield (j0, min(j0 + step, n),
+               None if diag_offset is None else int(diag_offset) - j0)
 
 
 def scaled_mm8(a8: torch.Tensor, b8_rowmajor: torch.Tensor,
@@ -903,6 +876,44 @@ def grad_gemms(bands, zimg: torch.Tensor, n: int, scale: torch.Tensor,
     if gt_full is None and on_dztxt is not None:
         on_dztxt(dztxt)
     return dzimg_acc.to(zimg.dtype), dztxt
+
+
+def band_grad_gemms(zimg: torch.Tensor, ztxt: torch.Tensor, step: int, emit,
+                    scale: torch.Tensor, *, diag_offset: Optional[int] = None,
+                    g_dtype=torch.bfloat16, with_gt: bool = False,
+                    qc: Optional[QuantCache] = None, on_dztxt=None,
+                    bf16_scale: bool = False):
+    """The column-banded recompute backward → ``(dzimg, dztxt)``: per band of
+    ``step`` columns, ``emit(j0, j1, diag_j, g, gt)`` writes dL/dlogit of
+    columns ``j0:j1`` into the ``(b, j1 − j0)`` slab ``g`` (and its transpose
+    into ``gt``, given ``with_gt``; ``None`` otherwise), and
+    :func:`grad_gemms` runs the band's two GEMMs (``scale``, ``on_dztxt``,
+    ``bf16_scale`` are its).  ``diag_j`` is ``diag_offset`` shifted to the
+    band, ``qc`` the per-tensor quantization whose text rows go with each
+    band.  ``step >= n`` is one band: a single :class:`GBand`, no fp32
+    accumulator."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    step = min(step, n)
+
+    def slabs(c):
+        return (torch.empty((b, c), device=zimg.device, dtype=g_dtype),
+                torch.empty((c, b), device=zimg.device, dtype=g_dtype)
+                if with_gt else None)
+
+    def bands():
+        # One reused slab (pair): grad_gemms consumes each band before it
+        # asks for the next, so the stream orders the kernel of band k+1
+        # after the GEMMs of band k.  This generator must stay lazy — a list
+        # of its bands would all alias the one slab.  A ragged last band gets
+        # a slab of its own width.
+        bufs = slabs(step)
+        for j0, j1, diag_j in col_bands(n, step, diag_offset):
+            g, gt = bufs if j1 - j0 == step else slabs(j1 - j0)
+            emit(j0, j1, diag_j, g, gt)
+            yield GBand(g, gt, ztxt[j0:j1], qc and qc.text_rows(j0, j1))
+
+    return grad_gemms(next(bands()) if step == n else bands(), zimg, n, scale,
+                      on_dztxt=on_dztxt, bf16_scale=bf16_scale)
 
 
 def scalar_grads(out3: torch.Tensor, go: torch.Tensor, t_eff: torch.Tensor,
@@ -1465,8 +1476,7 @@ def siglip_bwd_from_g(zimg: torch.Tensor, ztxt: torch.Tensor,
     b, d = zimg.shape
     n = ztxt.shape[0]
     t_true = _prep_scalar(t_prime, zimg.device).exp()
-    go = grad_output.detach().reshape(()).to(device=zimg.device,
-                                             dtype=torch.float32)
+    go = _go_scalar(grad_output, zimg.device)
     qc = qcache if quant in ("fp8", "mixed") else None
     t_eff = t_true
     if qc is not None and qc.rowwise:
@@ -1494,8 +1504,7 @@ def siglip_bwd_from_g_chunks(zimg: torch.Tensor, chunks, t_prime: torch.Tensor,
     shared), plus the one ``(n, b)`` transpose slab ``gt`` — dztxt is a single
     GEMM.  Same return contract as :func:`siglip_bwd_from_g`."""
     t_true = _prep_scalar(t_prime, zimg.device).exp()
-    go = grad_output.detach().reshape(()).to(device=zimg.device,
-                                             dtype=torch.float32)
+    go = _go_scalar(grad_output, zimg.device)
     dzimg, dztxt = grad_gemms(
         [GBand(g, None, zt, qc)
          for g, zt, qc in zip(g_chunks, chunks, qcaches)],
@@ -1516,8 +1525,7 @@ def siglip_bwd_banded(zimg: torch.Tensor, ztxt: torch.Tensor,
     the text rows in order): per-band GEMMs, still no recompute.  Same
     return contract as :func:`siglip_bwd_from_g`."""
     t_true = _prep_scalar(t_prime, zimg.device).exp()
-    go = grad_output.detach().reshape(()).to(device=zimg.device,
-                                             dtype=torch.float32)
+    go = _go_scalar(grad_output, zimg.device)
     bands, j0 = [], 0
     for g in slabs:
         bands.append(GBand(g, None, ztxt[j0:j0 + g.shape[1]]))

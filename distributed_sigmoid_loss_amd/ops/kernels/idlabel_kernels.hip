@@ -23,16 +23,17 @@
 //
 // Structure.  The tile, its main loop (text fragment first: lane l owns image
 // row (l & 15) and the four consecutive text columns 4·(l >> 4) … +3 of each
-// fragment), the block walk and the g write-out are pair_tile.h's; this file
-// adds the id staging and the epilogue.
+// fragment), the block walk, the id staging and the g
+// write-out are pair_tile.h's; this file adds the epilogue.
 //
 // Ids.  Once the K loop's last barrier has passed, the tile's 128 row ids and
-// 128 column ids are staged as int64 in the 2 KiB above the g staging area;
-// a row or column outside the block gets id −1 there, so padding is masked by
-// the same test as a negative id.  The mask matters: a zero-filled padding
-// element has z = bias, not 0, and would add softplus(bias) to the loss.  The
-// epilogue walks the fragments column-major, so a lane keeps its 4 row ids
-// in registers and reads the 4 column ids of one fragment at a time.
+// 128 column ids are staged as int64 (pair_tile.h's stage_ids) in the 2 KiB
+// above the g staging area; a row or column outside the block gets id −1
+// there, so padding is masked by the same test as a negative id.  The mask
+// matters: a zero-filled padding element has z = bias, not 0, and would add
+// softplus(bias) to the loss.  The epilogue walks the fragments column-major,
+// so a lane keeps its 4 row ids in registers and reads the 4 column ids of
+// one fragment at a time.
 //
 // exp / log are the bare v_exp_f32 / v_log_f32 (base 2) with the ln 2 factors
 // folded in; 1 / (1 + e) is v_rcp_f32 (1 ulp, 2⁻¹⁶ of a bf16 ulp).
@@ -42,7 +43,6 @@
 namespace {
 
 constexpr int IDS_OFF = G_STAGE_BYTES;        // 128 row ids, 128 column ids
-constexpr int IDS_BYTES = (BM + BN) * 8;      // 2 KiB
 constexpr int RED_OFF = IDS_OFF + IDS_BYTES;  // 4 waves × 3 partials
 
 static_assert(IDS_OFF % 16 == 0, "id staging must take 16-byte reads");
@@ -73,19 +73,8 @@ __launch_bounds__(NTHREADS) __global__ void sigmoid_ids_kernel(
   const float bs = bias[0];
   const bool ignore = ignore_dups != 0;
 
-  // Stage the tile's ids: threads 0..127 a row id, 128..255 a column id;
-  // −1 outside the block.
   long long* idl = reinterpret_cast<long long*>(lds + IDS_OFF);
-  {
-    const bool is_row = tid < BM;
-    const int e = is_row ? m0 + tid : n0 + (tid - BM);
-    const int len = is_row ? b : n;
-    const long long* src = is_row ? img_ids : txt_ids;
-    long long id = -1;
-    if (e < len) id = src[e];
-    idl[tid] = id;
-  }
-  __syncthreads();
+  stage_ids(idl, img_ids, txt_ids, m0, n0, b, n);
 
   // This lane's four rows: id, and the column of the row's positional
   // positive ("ignore" only; −1 when it has none inside the block).
@@ -104,13 +93,7 @@ __launch_bounds__(NTHREADS) __global__ void sigmoid_ids_kernel(
     const int lcol0 = wn * 64 + j * 16 + fq * 4;
     const int col0 = n0 + lcol0;
     long long cid[4];
-    {
-      const longlong2 c01 =
-          *reinterpret_cast<const longlong2*>(idl + BM + lcol0);
-      const longlong2 c23 =
-          *reinterpret_cast<const longlong2*>(idl + BM + lcol0 + 2);
-      cid[0] = c01.x; cid[1] = c01.y; cid[2] = c23.x; cid[3] = c23.y;
-    }
+    load_col_ids(idl, lcol0, cid);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       bf16x4 out;

@@ -1,7 +1,9 @@
 // The 128×128 pair tile shared by rank_kernels.hip, softmax_kernels.hip,
-// topk_kernels.hip and idlabel_kernels.hip (gfx950, MI355X): constants, the
-// block walk, the main loop that leaves a tile of <zimg_i, ztxt_j> dot
-// products in MFMA accumulators, and the helpers every epilogue needs.  Each
+// topk_kernels.hip, idlabel_kernels.hip and softmax_id_kernels.hip (gfx950,
+// MI355X): constants, the block walk, the main loop that leaves a tile of
+// <zimg_i, ztxt_j> dot products in MFMA accumulators, and the helpers the
+// epilogues share (the positive's column, the log-sum-exp guard, the sample-id
+// staging, the g write-out).  Each
 // including file adds its own epilogue and C entry points; nothing here is
 // exported.  Everything sits in an anonymous namespace, so each translation
 // unit gets its own copy.
@@ -220,6 +222,43 @@ __device__ __forceinline__ void pair_tile_dots(
 __device__ __forceinline__ int positive_col(int row, int diag, int n) {
   const long long pos = (long long)row + diag;
   return (diag != DIAG_NONE && pos >= 0 && pos < n) ? (int)pos : -1;
+}
+
+// The max subtracted in the exp(x − m) terms of a log-sum-exp: m == −inf
+// (nothing valid) is replaced by 0 so that the difference stays −inf instead
+// of becoming NaN.
+__device__ __forceinline__ float safe_max(float m) {
+  return m == -__builtin_inff() ? 0.f : m;
+}
+
+// Sample ids (idlabel_kernels.hip, softmax_id_kernels.hip).  Stage the tile's
+// ids in the IDS_BYTES at `idl`: threads 0..127 a row id, 128..255 a column
+// id; −1 outside the block, so padding is masked by the same test as a
+// negative id.  Ends on a barrier.
+constexpr int IDS_BYTES = (BM + BN) * 8;      // 2 KiB
+
+__device__ __forceinline__ void stage_ids(long long* idl,
+                                          const long long* __restrict__ img_ids,
+                                          const long long* __restrict__ txt_ids,
+                                          int m0, int n0, int b, int n) {
+  const int tid = threadIdx.x;
+  const bool is_row = tid < BM;
+  const int e = is_row ? m0 + tid : n0 + (tid - BM);
+  const int len = is_row ? b : n;
+  const long long* src = is_row ? img_ids : txt_ids;
+  long long id = -1;
+  if (e < len) id = src[e];
+  idl[tid] = id;
+  __syncthreads();
+}
+
+// The four column ids of fragment column lcol0 … +3.
+__device__ __forceinline__ void load_col_ids(const long long* idl, int lcol0,
+                                             long long (&cid)[4]) {
+  const longlong2 c01 = *reinterpret_cast<const longlong2*>(idl + BM + lcol0);
+  const longlong2 c23 =
+      *reinterpret_cast<const longlong2*>(idl + BM + lcol0 + 2);
+  cid[0] = c01.x; cid[1] = c01.y; cid[2] = c23.x; cid[3] = c23.y;
 }
 
 // Write-out of the bf16 g tile staged in `lds` ([BM] rows at G_PITCH bytes)

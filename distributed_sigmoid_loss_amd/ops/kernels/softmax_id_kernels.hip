@@ -38,14 +38,15 @@
 //
 // Structure.  The tile, its main loop (text fragment first: lane l owns image
 // row (l & 15) and the four consecutive text columns 4·(l >> 4) … +3 of each
-// fragment), the block walk and the g write-out are pair_tile.h's; this file
-// adds the id staging and the epilogues.
+// fragment), the block walk, the id staging and the g
+// write-out are pair_tile.h's; this file adds the epilogues.
 //
 // Ids.  Once the K loop's last barrier has passed, the tile's 128 row ids and
-// 128 column ids are staged as int64 in LDS; a row or column outside the
-// block gets id −1 there, so padding is masked by the same test as a negative
-// id.  The epilogues walk the fragments column-major, so a lane keeps its 4
-// row ids in registers and reads the 4 column ids of one fragment at a time.
+// 128 column ids are staged as int64 in LDS (stage_ids); a row or column
+// outside the block gets id −1 there, so padding is masked by the same test
+// as a negative id.  The epilogues walk the fragments column-major, so a lane
+// keeps its 4 row ids in registers and reads the 4 column ids of one fragment
+// at a time.
 //
 // Masking.  A masked element becomes −inf before the max and the sum, by a
 // select; a partial over masked elements alone is (−inf, 0) with positive
@@ -69,7 +70,6 @@ struct __attribute__((aligned(16))) Partial {
 };
 static_assert(sizeof(Partial) == 16, "one 16-byte store per record");
 
-constexpr int IDS_BYTES = (BM + BN) * 8;              // 2 KiB
 constexpr int LSE_IDS_OFF = 0;
 constexpr int LSE_PART_OFF = LSE_IDS_OFF + IDS_BYTES;  // 2·(BM + BN) records
 static_assert(LSE_PART_OFF % 16 == 0, "records take 16-byte accesses");
@@ -81,38 +81,6 @@ constexpr int G_IDS_OFF = G_STAGE_BYTES;
 constexpr int G_RED_OFF = G_IDS_OFF + IDS_BYTES;
 static_assert(G_IDS_OFF % 16 == 0, "id staging must take 16-byte reads");
 static_assert(G_RED_OFF + 16 <= 2 * BUF_BYTES, "epilogue staging exceeds LDS");
-
-// exp(x − m) terms of a log-sum-exp in base 2: m == −inf (nothing unmasked)
-// is replaced by 0 so that the difference stays −inf instead of becoming NaN.
-__device__ __forceinline__ float safe_max(float m) {
-  return m == -__builtin_inff() ? 0.f : m;
-}
-
-// Stage the tile's ids: threads 0..127 a row id, 128..255 a column id; −1
-// outside the block.  Ends on a barrier.
-__device__ __forceinline__ void stage_ids(long long* idl,
-                                          const long long* __restrict__ img_ids,
-                                          const long long* __restrict__ txt_ids,
-                                          int m0, int n0, int b, int n) {
-  const int tid = threadIdx.x;
-  const bool is_row = tid < BM;
-  const int e = is_row ? m0 + tid : n0 + (tid - BM);
-  const int len = is_row ? b : n;
-  const long long* src = is_row ? img_ids : txt_ids;
-  long long id = -1;
-  if (e < len) id = src[e];
-  idl[tid] = id;
-  __syncthreads();
-}
-
-// The four column ids of fragment column lcol0 … +3.
-__device__ __forceinline__ void load_col_ids(const long long* idl, int lcol0,
-                                             long long (&cid)[4]) {
-  const longlong2 c01 = *reinterpret_cast<const longlong2*>(idl + BM + lcol0);
-  const longlong2 c23 =
-      *reinterpret_cast<const longlong2*>(idl + BM + lcol0 + 2);
-  cid[0] = c01.x; cid[1] = c01.y; cid[2] = c23.x; cid[3] = c23.y;
-}
 
 // Two waves per SIMD asked for: two workgroups share a CU (64 KiB of LDS
 // each), which is 256 registers per lane; left alone the scheduler spends

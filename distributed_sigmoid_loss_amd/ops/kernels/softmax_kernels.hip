@@ -44,12 +44,7 @@ namespace {
 static_assert(G_STAGE_BYTES + 16 <= 2 * BUF_BYTES, "g staging exceeds LDS");
 
 // exp(x − m) terms of a log-sum-exp in base 2: `sc2` is t·log2 e, `m` a raw
-// dot product; m == −inf (nothing valid) is replaced by 0 so that the
-// difference stays −inf instead of becoming NaN.
-__device__ __forceinline__ float safe_max(float m) {
-  return m == -__builtin_inff() ? 0.f : m;
-}
-
+// dot product, guarded by pair_tile.h's safe_max.
 __launch_bounds__(NTHREADS) __global__ void softmax_lse_partials_kernel(
     const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt,
     const float* __restrict__ tprime, float2* __restrict__ row_ws,

@@ -37,6 +37,12 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
   of ``−log softmax``, masked pairs out of both normalisers), from a fused
   HIP kernel pair that adds positive sums and counts to the log-sum-exp pass;
   ``DistributedSoftmaxLoss`` takes ``image_ids`` / ``text_ids``.
+- ``retrieval_ranks_ids`` / ``distributed_retrieval_ranks_ids`` — retrieval
+  ranks under the same sample-ID labels: the rank of each sample's best
+  matching partner among its non-matching ones (several captions per image,
+  duplicates ignored, padding left out), from two fused HIP passes —
+  ``pair_best_positive_ids``, which skips the tiles without a positive, and
+  ``pair_rank_counts_ids``.
 
 The compute path is PyTorch-ROCm + HIP/CDNA4 kernels + RCCL over xGMI; there
 are no CUDA compatibility layers and no multi-backend dispatch.
@@ -58,6 +64,10 @@ from .losses.retrieval import (
     merge_topk,
     retrieval_topk,
     distributed_retrieval_topk,
+    pair_best_positive_ids,
+    pair_rank_counts_ids,
+    retrieval_ranks_ids,
+    distributed_retrieval_ranks_ids,
 )
 from .losses.softmax_loss import (
     DistributedSoftmaxLoss,
@@ -88,6 +98,10 @@ __all__ = [
     "merge_topk",
     "retrieval_topk",
     "distributed_retrieval_topk",
+    "pair_best_positive_ids",
+    "pair_rank_counts_ids",
+    "retrieval_ranks_ids",
+    "distributed_retrieval_ranks_ids",
     "DistributedSoftmaxLoss",
     "softmax_contrastive_loss",
     "softmax_contrastive_loss_ids",

@@ -395,3 +395,246 @@ def distributed_retrieval_topk(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
         zi_all = all_gather_with_grad(zimg.detach(), group)
         t2i = pair_topk(ztxt.detach(), zi_all, k, off, impl=impl)
     return i2t, t2i
+
+
+# -- sample-ID labels -------------------------------------------------------
+#
+# With int64 sample ids (``losses/id_labels.py``: a negative id masks its row
+# or column; ``"positive"``: equal ids are positives; ``"ignore"``: the
+# positive is ``j == i + diag_offset`` and other equal-id pairs are masked) a
+# row may have several positives, or none.  The rank reported is that of the
+# row's BEST positive among its negatives:
+#
+#     row_best_i  = max_{j positive, not masked} s_ij      (−inf if none)
+#     rank_i2t[i] = #{ j negative : s_ij > row_best_i }    (−1 if none)
+#
+# and the column analogue.  Two passes over the grid: the best positives
+# (``ops.pair_best_positive_ids``, which skips the tiles whose ids hold no
+# positive), then the counts over the negatives thresholded at them
+# (``ops.pair_rank_counts_ids``).  Bests compose by ``max`` and counts by
+# ``+`` over column chunks and ranks, both exactly.
+
+def _id_block(zimg, ztxt, img_ids, txt_ids, duplicates, diag_offset):
+    from .id_labels import _DUPLICATES, _ids_vector
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings, got "
+            f"{tuple(zimg.shape)} and {tuple(ztxt.shape)}")
+    if zimg.shape[0] < 1 or ztxt.shape[0] < 1:
+        raise RuntimeError("the pair grid needs a non-empty block")
+    if duplicates not in _DUPLICATES:
+        raise ValueError(f"unknown duplicates {duplicates!r}")
+    img_ids = _ids_vector("img_ids", img_ids, zimg.shape[0], zimg.device)
+    txt_ids = _ids_vector("txt_ids", txt_ids, ztxt.shape[0], zimg.device)
+    return img_ids, txt_ids, diag_offset if duplicates == "ignore" else None
+
+
+def _id_impl(impl, zimg, ztxt):
+    if impl == "auto":
+        impl = ("hip" if zimg.is_cuda and zimg.dtype == torch.bfloat16
+                and ztxt.dtype == torch.bfloat16 else "torch")
+    if impl not in ("hip", "torch"):
+        raise ValueError(f"unknown impl {impl!r}")
+    return impl
+
+
+def _row_chunks(zimg, ztxt, img_ids, txt_ids, duplicates, diag_offset,
+                row_chunk):
+    """``(r0, r1, scores, positive, negative)`` per chunk of rows, the last
+    two with the masked pairs taken out."""
+    from .id_labels import pair_classes
+    cdt = _compute_dtype(zimg)
+    zt = ztxt.detach().to(cdt)
+    step = max(1, int(row_chunk))
+    for r0 in range(0, zimg.shape[0], step):
+        r1 = min(zimg.shape[0], r0 + step)
+        s = zimg[r0:r1].detach().to(cdt) @ zt.T
+        # pair_classes counts rows from 0: move the diagonal instead.
+        pos, masked = pair_classes(
+            img_ids[r0:r1], txt_ids, duplicates,
+            None if diag_offset is None else int(diag_offset) + r0)
+        yield r0, r1, s, pos & ~masked, ~pos & ~masked
+
+
+def _torch_best_side(name, on, best, length, device, cdt):
+    if not on:
+        if best is not None:
+            raise RuntimeError(f"{name}_best given with {name}s=False")
+        return None
+    if best is None:
+        return torch.full((length,), -math.inf, device=device, dtype=cdt)
+    if best.shape != (length,) or not best.is_floating_point():
+        raise RuntimeError(
+            f"{name}_best must be floating point of shape ({length},), got "
+            f"{best.dtype} {tuple(best.shape)}")
+    return best
+
+
+def pair_best_positive_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                           img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                           duplicates: str = "positive",
+                           diag_offset: Optional[int] = None,
+                           row_best: Optional[torch.Tensor] = None,
+                           col_best: Optional[torch.Tensor] = None,
+                           rows: bool = True, cols: bool = True,
+                           impl: str = "auto",
+                           row_chunk: int = _TORCH_ROW_CHUNK):
+    """Best positive score per row and per column under sample-ID labels →
+    ``(row_best | None, col_best | None)``: ``row_best[i] = max(row_best[i],
+    max s_ij over the positives j of row i that are not masked)``, ``−inf``
+    where there is none, and the column analogue.
+
+    Results are max-accumulated into ``row_best`` / ``col_best`` when given
+    (the caller fills them with ``−inf``) and start from fresh ``−inf``
+    otherwise, so calls over column chunks ``ztxt[j0:j1]``, ``txt_ids[j0:j1]``
+    with ``diag_offset − j0`` compose.  ``diag_offset`` is read with
+    ``duplicates="ignore"`` only.  A side switched off is ``None``.
+
+    ``impl``: ``auto`` (``hip`` on GPU for bf16, ``torch`` elsewhere) |
+    ``hip`` (bf16, ``d % 8 == 0``, fp32 results; raises without the built
+    extension) | ``torch`` (row-chunked composite; fp32, fp64 for fp64
+    inputs)."""
+    img_ids, txt_ids, diag_offset = _id_block(zimg, ztxt, img_ids, txt_ids,
+                                              duplicates, diag_offset)
+    if _id_impl(impl, zimg, ztxt) == "hip":
+        from .. import ops
+        return ops.pair_best_positive_ids(zimg, ztxt, img_ids, txt_ids,
+                                          duplicates, diag_offset, row_best,
+                                          col_best, rows, cols)
+    b, n, dev = zimg.shape[0], ztxt.shape[0], zimg.device
+    cdt = _compute_dtype(zimg)
+    row_best = _torch_best_side("row", rows, row_best, b, dev, cdt)
+    col_best = _torch_best_side("col", cols, col_best, n, dev, cdt)
+    if row_best is None and col_best is None:
+        return None, None
+    for r0, r1, s, pos, _ in _row_chunks(zimg, ztxt, img_ids, txt_ids,
+                                         duplicates, diag_offset, row_chunk):
+        s = s.masked_fill(~pos, -math.inf)
+        if row_best is not None:
+            row_best[r0:r1] = torch.maximum(row_best[r0:r1],
+                                            s.amax(1).to(row_best.dtype))
+        if col_best is not None:
+            col_best.copy_(torch.maximum(col_best,
+                                         s.amax(0).to(col_best.dtype)))
+    return row_best, col_best
+
+
+def pair_rank_counts_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                         row_thr: Optional[torch.Tensor],
+                         col_thr: Optional[torch.Tensor],
+                         img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                         duplicates: str = "positive",
+                         diag_offset: Optional[int] = None,
+                         row_cnt: Optional[torch.Tensor] = None,
+                         col_cnt: Optional[torch.Tensor] = None,
+                         impl: str = "auto",
+                         row_chunk: int = _TORCH_ROW_CHUNK):
+    """:func:`pair_rank_counts` over the negatives of sample-ID labels →
+    ``(row_cnt | None, col_cnt | None)``, int32: ``row_cnt[i] += #{j negative
+    : s_ij > row_thr[i]}``, ``col_cnt[j] += #{i negative : s_ij >
+    col_thr[j]}`` (strict ``>``).  A pair is negative when both ids are ``≥
+    0`` and different and, with ``duplicates="ignore"``, it is not ``j == i +
+    diag_offset``.  Thresholds, accumulation, side omission and ``impl`` as
+    in :func:`pair_rank_counts` and :func:`pair_best_positive_ids`."""
+    img_ids, txt_ids, diag_offset = _id_block(zimg, ztxt, img_ids, txt_ids,
+                                              duplicates, diag_offset)
+    if _id_impl(impl, zimg, ztxt) == "hip":
+        from .. import ops
+        return ops.pair_rank_counts_ids(zimg, ztxt, row_thr, col_thr, img_ids,
+                                        txt_ids, duplicates, diag_offset,
+                                        row_cnt, col_cnt)
+    b, n, dev = zimg.shape[0], ztxt.shape[0], zimg.device
+    cdt = _compute_dtype(zimg)
+    row_cnt = _check_side("row", row_thr, row_cnt, b, dev)
+    col_cnt = _check_side("col", col_thr, col_cnt, n, dev)
+    if row_cnt is None and col_cnt is None:
+        return None, None
+    rthr = None if row_thr is None else row_thr.detach().to(cdt)
+    cthr = None if col_thr is None else col_thr.detach().to(cdt)
+    for r0, r1, s, _, neg in _row_chunks(zimg, ztxt, img_ids, txt_ids,
+                                         duplicates, diag_offset, row_chunk):
+        s = s.masked_fill(~neg, -math.inf)
+        if rthr is not None:
+            row_cnt[r0:r1] += (s > rthr[r0:r1, None]).sum(1, dtype=torch.int32)
+        if cthr is not None:
+            col_cnt += (s > cthr[None, :]).sum(0, dtype=torch.int32)
+    return row_cnt, col_cnt
+
+
+def _ranks_from(best: torch.Tensor, cnt: torch.Tensor) -> torch.Tensor:
+    return torch.where(best == -math.inf, torch.full_like(cnt, -1), cnt).long()
+
+
+def retrieval_ranks_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                        img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                        duplicates: str = "positive",
+                        diag_offset: Optional[int] = 0,
+                        impl: str = "auto") -> RetrievalRanks:
+    """Retrieval ranks under sample-ID labels: for image ``i`` the number of
+    non-matching texts that score above its best matching text, for text
+    ``j`` the number of non-matching images above its best matching image;
+    ``-1`` for a row or column without a positive (a masked one included).
+    One :func:`pair_best_positive_ids` pass and one
+    :func:`pair_rank_counts_ids` pass thresholded at it.
+
+    With ``img_ids = arange(b) + diag`` (``diag ≥ 0``; a negative id would
+    mask its row) and ``txt_ids = arange(n)`` these are the ranks of
+    ``retrieval_ranks(diag_offset=diag)``; so are those of ``"ignore"`` at
+    ``diag_offset=diag`` with ids that are all distinct."""
+    row_best, col_best = pair_best_positive_ids(
+        zimg, ztxt, img_ids, txt_ids, duplicates, diag_offset, impl=impl)
+    row_cnt, col_cnt = pair_rank_counts_ids(
+        zimg, ztxt, row_best, col_best, img_ids, txt_ids, duplicates,
+        diag_offset, impl=impl)
+    return RetrievalRanks(_ranks_from(row_best, row_cnt),
+                          _ranks_from(col_best, col_cnt))
+
+
+def distributed_retrieval_ranks_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                                    image_ids: torch.Tensor,
+                                    text_ids: torch.Tensor,
+                                    duplicates: str = "positive", group=None,
+                                    impl: str = "auto") -> RetrievalRanks:
+    """:func:`retrieval_ranks_ids` of this rank's ``b`` images against all
+    ``W·b`` texts and of its ``b`` texts against all ``W·b`` images (equal
+    ``b`` on every rank; with ``"ignore"`` the positive of local image ``i``
+    is local text ``i``).
+
+    The text shard and the text ids are all-gathered.  The best-positive pass
+    over the ``(b, W·b)`` block with ``diag_offset = rank·b`` completes the
+    row bests; the column bests are all-reduced with ``MAX`` (exact in fp32).
+    The count pass completes the row counts; the column counts are summed
+    across ranks and the local slice kept.  World size 1 is
+    :func:`retrieval_ranks_ids`."""
+    if (not dist.is_available() or not dist.is_initialized()
+            or dist.get_world_size(group) == 1):
+        return retrieval_ranks_ids(zimg, ztxt, image_ids, text_ids,
+                                   duplicates, 0, impl=impl)
+    from .id_labels import _ids_vector
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    b = zimg.shape[0]
+    if ztxt.shape[0] != b:
+        raise RuntimeError(
+            "distributed_retrieval_ranks_ids needs paired shards")
+    text_ids = _ids_vector("text_ids", text_ids, b, zimg.device)
+    with torch.no_grad():
+        zt_all = all_gather_with_grad(ztxt.detach(), group)
+        ids_all = torch.empty(world * b, device=text_ids.device,
+                              dtype=text_ids.dtype)
+        dist.all_gather_into_tensor(ids_all, text_ids, group=group)
+        row_best, col_best = pair_best_positive_ids(
+            zimg, zt_all, image_ids, ids_all, duplicates, rank * b, impl=impl)
+        dist.all_reduce(col_best, op=dist.ReduceOp.MAX, group=group)
+        row_cnt, col_cnt = pair_rank_counts_ids(
+            zimg, zt_all, row_best, col_best, image_ids, ids_all, duplicates,
+            rank * b, impl=impl)
+        if _backend_is_gloo(group):
+            dist.all_reduce(col_cnt, op=dist.ReduceOp.SUM, group=group)
+            local = col_cnt[rank * b:(rank + 1) * b]
+        else:
+            local = torch.empty(b, device=col_cnt.device, dtype=col_cnt.dtype)
+            dist.reduce_scatter_tensor(local, col_cnt, op=dist.ReduceOp.SUM,
+                                       group=group)
+    sl = slice(rank * b, (rank + 1) * b)
+    return RetrievalRanks(_ranks_from(row_best, row_cnt),
+                          _ranks_from(col_best[sl], local))

@@ -47,6 +47,11 @@ exposes:
   several positives per row and masked pairs at exactly 0
   (``losses/softmax_loss.py`` builds the multi-positive InfoNCE loss on
   them).
+- sample-ID labels for the retrieval ranks: :func:`pair_best_positive_ids`
+  — the best unmasked positive score of every row and column, skipping the
+  tiles whose ids hold no positive — and :func:`pair_rank_counts_ids` — the
+  threshold counts over the negatives only (``losses/retrieval.py`` builds
+  the multi-positive ranks and their distributed form on them).
 
 Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
@@ -199,6 +204,12 @@ _EXPORTS = {
     # (stream, zimg, ztxt, t', img_ids, txt_ids, row_lse, row_w, row_pw,
     #  col_lse, col_w, col_pw, g, gs_ws, b, n, d, ldg, diag, mode)
     "softmax_ids_g_bf16": [_P] * 14 + [_I] * 3 + [_L] + [_I] * 2,
+    # (stream, zimg, ztxt, img_ids, txt_ids, row_best, col_best, b, n, d,
+    #  diag, mode)
+    "pair_best_positive_ids_bf16": [_P] * 7 + [_I] * 5,
+    # (stream, zimg, ztxt, row_thr, col_thr, img_ids, txt_ids, row_cnt,
+    #  col_cnt, b, n, d, diag, mode)
+    "pair_rank_counts_ids_bf16": [_P] * 9 + [_I] * 5,
 }
 
 
@@ -1286,6 +1297,102 @@ def sigmoid_ids(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
         _DUPLICATES[duplicates]),
         "sigmoid_ids_bf16")
     return partials, g
+
+
+def _best_side(name: str, on: bool, best, length: int, device):
+    """One side (rows or columns) of :func:`pair_best_positive_ids`: the
+    caller's accumulator after validation, fresh ``−inf``, or ``None`` for a
+    side that is switched off."""
+    if not on:
+        if best is not None:
+            raise RuntimeError(f"{name}_best given with {name}s=False")
+        return None
+    if best is None:
+        return torch.full((length,), float("-inf"), device=device,
+                          dtype=torch.float32)
+    if not _vec_ok(best, torch.float32, length, device):
+        raise RuntimeError(
+            f"{name}_best must be a contiguous fp32 ({length},) tensor on "
+            f"{device} (got {best.dtype} {tuple(best.shape)} on "
+            f"{best.device})")
+    return best
+
+
+def pair_best_positive_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                           img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                           duplicates: str = "positive",
+                           diag_offset: Optional[int] = None,
+                           row_best: Optional[torch.Tensor] = None,
+                           col_best: Optional[torch.Tensor] = None,
+                           rows: bool = True, cols: bool = True):
+    """Best positive score of every row and column of the ``(b, n)`` score
+    grid ``s = zimg @ ztxtᵀ`` under sample-ID labels, without materializing
+    it → ``(row_best | None, col_best | None)``, fp32:
+
+    ``row_best[i] = max(row_best[i], max_{j ∈ P_i} s_ij)`` with ``P_i`` the
+    positives of row ``i`` that are not masked (the pair classes of
+    :func:`sigmoid_ids`), and the column analogue; ``−inf`` where there is
+    none.  The result is max-ACCUMULATED into ``row_best`` / ``col_best``
+    when given (the caller fills them with ``−inf``), so column chunks
+    (``ztxt[j0:j1]``, ``txt_ids[j0:j1]``, ``diag_offset − j0``), repeated
+    calls and ranks compose by ``max``; otherwise they start from ``−inf``
+    allocated here.  A side switched off (``rows=False`` / ``cols=False``) is
+    skipped and returned as ``None``.
+
+    A tile whose ids show that it holds no unmasked positive returns before
+    it reads the embeddings, so the cost follows the number of tiles that
+    hold one.  Integer-ordered atomics on the fp32 bit pattern: bitwise
+    reproducible.  No autograd."""
+    zi, zt, b, n, d, dev = _pair_block("pair_best_positive_ids", zimg, ztxt)
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
+    row_best = _best_side("row", rows, row_best, b, dev)
+    col_best = _best_side("col", cols, col_best, n, dev)
+    lib = _require_lib()
+    if row_best is None and col_best is None:
+        return None, None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.pair_best_positive_ids_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(img_ids),
+        _ptr(txt_ids), _ptr(row_best), _ptr(col_best), b, n, d,
+        _diag_arg(diag_offset), _DUPLICATES[duplicates]),
+        "pair_best_positive_ids_bf16")
+    return row_best, col_best
+
+
+def pair_rank_counts_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                         row_thr: Optional[torch.Tensor],
+                         col_thr: Optional[torch.Tensor],
+                         img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                         duplicates: str = "positive",
+                         diag_offset: Optional[int] = None,
+                         row_cnt: Optional[torch.Tensor] = None,
+                         col_cnt: Optional[torch.Tensor] = None):
+    """:func:`pair_rank_counts` under sample-ID labels →
+    ``(row_cnt | None, col_cnt | None)``:
+
+    ``row_cnt[i] += #{j negative : s_ij > row_thr[i]}`` and ``col_cnt[j] +=
+    #{i negative : s_ij > col_thr[j]}`` (strict ``>``), where a pair is
+    negative when it is neither masked nor positive (the pair classes of
+    :func:`sigmoid_ids`): both ids ``≥ 0`` and different, and with
+    ``duplicates="ignore"`` also off the diagonal ``j == i + diag_offset``.
+    Thresholds, counts, accumulation and side omission are those of
+    :func:`pair_rank_counts`.  Integer atomics only: bitwise reproducible.
+    No autograd."""
+    zi, zt, b, n, d, dev = _pair_block("pair_rank_counts_ids", zimg, ztxt)
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
+    lib = _require_lib()
+    row_thr, row_cnt = _rank_side("row", row_thr, row_cnt, b, dev)
+    col_thr, col_cnt = _rank_side("col", col_thr, col_cnt, n, dev)
+    if row_thr is None and col_thr is None:
+        return None, None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.pair_rank_counts_ids_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(row_thr),
+        _ptr(col_thr), _ptr(img_ids), _ptr(txt_ids), _ptr(row_cnt),
+        _ptr(col_cnt), b, n, d, _diag_arg(diag_offset),
+        _DUPLICATES[duplicates]),
+        "pair_rank_counts_ids_bf16")
+    return row_cnt, col_cnt
 
 
 class PairLseIds(NamedTuple):

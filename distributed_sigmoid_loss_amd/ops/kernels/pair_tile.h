@@ -1,9 +1,9 @@
 // The 128×128 pair tile shared by rank_kernels.hip, softmax_kernels.hip,
-// topk_kernels.hip, idlabel_kernels.hip and softmax_id_kernels.hip (gfx950,
-// MI355X): constants, the block walk, the main loop that leaves a tile of
-// <zimg_i, ztxt_j> dot products in MFMA accumulators, and the helpers the
-// epilogues share (the positive's column, the log-sum-exp guard, the sample-id
-// staging, the g write-out).  Each
+// topk_kernels.hip, idlabel_kernels.hip, softmax_id_kernels.hip and
+// rank_id_kernels.hip (gfx950, MI355X): constants, the block walk, the main
+// loop that leaves a tile of <zimg_i, ztxt_j> dot products in MFMA
+// accumulators, and the helpers the epilogues share (the positive's column,
+// the log-sum-exp guard, the sample-id staging, the g write-out).  Each
 // including file adds its own epilogue and C entry points; nothing here is
 // exported.  Everything sits in an anonymous namespace, so each translation
 // unit gets its own copy.
@@ -231,7 +231,8 @@ __device__ __forceinline__ float safe_max(float m) {
   return m == -__builtin_inff() ? 0.f : m;
 }
 
-// Sample ids (idlabel_kernels.hip, softmax_id_kernels.hip).  Stage the tile's
+// Sample ids (idlabel_kernels.hip, softmax_id_kernels.hip,
+// rank_id_kernels.hip).  Stage the tile's
 // ids in the IDS_BYTES at `idl`: threads 0..127 a row id, 128..255 a column
 // id; −1 outside the block, so padding is masked by the same test as a
 // negative id.  Ends on a barrier.
@@ -259,6 +260,15 @@ __device__ __forceinline__ void load_col_ids(const long long* idl, int lcol0,
   const longlong2 c23 =
       *reinterpret_cast<const longlong2*>(idl + BM + lcol0 + 2);
   cid[0] = c01.x; cid[1] = c01.y; cid[2] = c23.x; cid[3] = c23.y;
+}
+
+// The four row ids of fragment rows lrow0 … +3 (lrow0 % 4 == 0): what a lane
+// owns in the !TEXT_FIRST layout.
+__device__ __forceinline__ void load_row_ids(const long long* idl, int lrow0,
+                                             long long (&rid)[4]) {
+  const longlong2 r01 = *reinterpret_cast<const longlong2*>(idl + lrow0);
+  const longlong2 r23 = *reinterpret_cast<const longlong2*>(idl + lrow0 + 2);
+  rid[0] = r01.x; rid[1] = r01.y; rid[2] = r23.x; rid[3] = r23.y;
 }
 
 // Write-out of the bf16 g tile staged in `lds` ([BM] rows at G_PITCH bytes)

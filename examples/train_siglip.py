@@ -31,7 +31,9 @@ scores, image→text and text→image, over the global batch.
 ``batch-per-gpu / C`` images, each repeated ``C`` times against ``C`` distinct
 texts, and the sample ids (global sample index // C) tell the loss that all
 ``C`` pairs of an image are positives.  Needs ``--loss sigmoid --strategy
-all_gather --quant bf16``.
+all_gather --quant bf16``.  ``--eval-every`` then reports the ranks under the
+same ids (``distributed_retrieval_ranks_ids``): the other captions of an
+image no longer count against it.  ``--hard-negatives`` stays positional.
 """
 
 from __future__ import annotations
@@ -50,6 +52,7 @@ from distributed_sigmoid_loss_amd import (
     DistributedSigmoidLoss,
     DistributedSoftmaxLoss,
     distributed_retrieval_ranks,
+    distributed_retrieval_ranks_ids,
     distributed_retrieval_topk,
     positive_scores,
     recall_at_k,
@@ -169,7 +172,12 @@ def main():
         if args.eval_every > 0 and (step + 1) % args.eval_every == 0:
             # Collective: every rank takes part, rank 0 reports its shard's
             # ranks against the global batch.
-            ranks = distributed_retrieval_ranks(zi.detach(), zt.detach())
+            # With several captions per image the ranks follow the training
+            # ids: the best matching caption among the non-matching ones.
+            ranks = (distributed_retrieval_ranks(zi.detach(), zt.detach())
+                     if ids is None else
+                     distributed_retrieval_ranks_ids(zi.detach(), zt.detach(),
+                                                     ids, ids))
             if rank == 0:
                 r_i2t, r_t2i = recall_at_k(ranks.i2t, (1, 5)), \
                     recall_at_k(ranks.t2i, (1, 5))

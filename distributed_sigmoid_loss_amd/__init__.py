@@ -43,6 +43,12 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
   duplicates ignored, padding left out), from two fused HIP passes —
   ``pair_best_positive_ids``, which skips the tiles without a positive, and
   ``pair_rank_counts_ids``.
+- ``pair_topk_ids`` / ``retrieval_topk_ids`` /
+  ``distributed_retrieval_topk_ids`` — top-k and hard-negative mining under
+  the same sample-ID labels: the candidates are the labels' negatives, so no
+  other caption of the same image, repeated sample or padding column is
+  returned as a "hard negative"; a fused HIP kernel that turns the ids into
+  per-lane class bits before each tile's dot products.
 
 The compute path is PyTorch-ROCm + HIP/CDNA4 kernels + RCCL over xGMI; there
 are no CUDA compatibility layers and no multi-backend dispatch.
@@ -68,6 +74,9 @@ from .losses.retrieval import (
     pair_rank_counts_ids,
     retrieval_ranks_ids,
     distributed_retrieval_ranks_ids,
+    pair_topk_ids,
+    retrieval_topk_ids,
+    distributed_retrieval_topk_ids,
 )
 from .losses.softmax_loss import (
     DistributedSoftmaxLoss,
@@ -102,6 +111,9 @@ __all__ = [
     "pair_rank_counts_ids",
     "retrieval_ranks_ids",
     "distributed_retrieval_ranks_ids",
+    "pair_topk_ids",
+    "retrieval_topk_ids",
+    "distributed_retrieval_topk_ids",
     "DistributedSoftmaxLoss",
     "softmax_contrastive_loss",
     "softmax_contrastive_loss_ids",

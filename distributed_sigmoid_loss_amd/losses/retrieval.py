@@ -29,7 +29,9 @@ so results are bitwise reproducible and :func:`merge_topk` of results over
 disjoint column chunks equals the single call.  On GPU the lists come from
 the fused HIP kernel (``ops.pair_topk``) in one pass over the grid;
 :func:`retrieval_topk` runs both directions, :func:`distributed_retrieval_topk`
-the global batch.
+the global batch.  With sample-ID labels the candidates are the labels'
+negatives (:func:`pair_topk_ids`, ``ops.pair_topk_ids``,
+:func:`retrieval_topk_ids`, :func:`distributed_retrieval_topk_ids`).
 """
 
 from __future__ import annotations
@@ -638,3 +640,138 @@ def distributed_retrieval_ranks_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
     sl = slice(rank * b, (rank + 1) * b)
     return RetrievalRanks(_ranks_from(row_best, row_cnt),
                           _ranks_from(col_best[sl], local))
+
+
+# -- top-k under sample-ID labels -------------------------------------------
+#
+# The candidates of a row are the NEGATIVES of the labels — neither masked
+# nor positive — so the lists are hard negatives that hold no other caption
+# of the row's image, no repeated sample and no padding column, and a masked
+# row gets none.  Order, fill, ``col_base`` and merging are :func:`pair_topk`'s.
+
+def _torch_pair_topk_ids(zimg, ztxt, k, img_ids, txt_ids, duplicates,
+                         diag_offset, row_chunk=_TORCH_ROW_CHUNK):
+    """Row-chunked torch composite with the contract of the kernel: scores
+    off the negatives become ``−inf``, a stable descending sort keeps the
+    lower column first, ``−inf`` slots become ``(−inf, −1)``."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    dev = zimg.device
+    scores = torch.full((b, k), -math.inf, device=dev,
+                        dtype=_compute_dtype(zimg))
+    cols = torch.full((b, k), -1, device=dev, dtype=torch.long)
+    kk = min(k, n)
+    for r0, r1, s, _, neg in _row_chunks(zimg, ztxt, img_ids, txt_ids,
+                                         duplicates, diag_offset, row_chunk):
+        s = s.masked_fill(~neg, -math.inf)
+        top_s, top_c = torch.sort(s, dim=1, descending=True, stable=True)
+        top_s, top_c = top_s[:, :kk], top_c[:, :kk]
+        scores[r0:r1, :kk] = top_s
+        cols[r0:r1, :kk] = torch.where(top_s == -math.inf,
+                                       torch.full_like(top_c, -1), top_c)
+    return scores, cols
+
+
+def pair_topk_ids(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
+                  img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                  duplicates: str = "positive",
+                  diag_offset: Optional[int] = None, col_base: int = 0,
+                  impl: str = "auto") -> TopK:
+    """:func:`pair_topk` over the negatives of sample-ID labels: the ``k``
+    best scoring columns of every row among the pairs whose ids are both ``≥
+    0`` and different and which, with ``duplicates="ignore"``, are not ``j ==
+    i + diag_offset`` (``diag_offset`` is read in that mode only).  Order,
+    ``(−inf, −1)`` fill, ``col_base`` and "no autograd" as in
+    :func:`pair_topk`; a masked row is all fill.
+
+    A chunked call is ``pair_topk_ids(zimg, ztxt[j0:j1], k, img_ids,
+    txt_ids[j0:j1], duplicates, diag_offset − j0, col_base=j0)`` per chunk
+    and one :func:`merge_topk`.  With ``img_ids = arange(b) + diag`` (``diag ≥
+    0``), ``txt_ids = arange(n)`` this is ``pair_topk(diag_offset=diag)``; so
+    is ``"ignore"`` at ``diag_offset`` with ids that are all distinct.
+
+    ``impl``: ``auto`` (``hip`` on GPU for bf16 inputs and ``k`` within the
+    kernel's range, ``torch`` otherwise) | ``hip`` (bf16, ``d % 8 == 0``,
+    ``k ≤ ops.pair_topk_max_k()``; raises otherwise) | ``torch`` (row-chunked
+    composite, any ``k``)."""
+    img_ids, txt_ids, diag_offset = _id_block(zimg, ztxt, img_ids, txt_ids,
+                                              duplicates, diag_offset)
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    auto = impl == "auto"
+    impl = _id_impl(impl, zimg, ztxt)
+    if impl == "hip":
+        from .. import ops
+        if auto and k > ops.pair_topk_max_k():
+            impl = "torch"
+    if impl == "hip":
+        scores, cols = ops.pair_topk_ids(zimg, ztxt, k, img_ids, txt_ids,
+                                         duplicates, diag_offset)
+        cols = cols.long()
+    else:
+        scores, cols = _torch_pair_topk_ids(zimg, ztxt, k, img_ids, txt_ids,
+                                            duplicates, diag_offset)
+    if col_base:
+        cols = torch.where(cols >= 0, cols + int(col_base), cols)
+    return TopK(scores, cols)
+
+
+def retrieval_topk_ids(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
+                       img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                       duplicates: str = "positive",
+                       diag_offset: Optional[int] = 0, impl: str = "auto"):
+    """``(i2t, t2i)``: for every image its ``k`` hardest negative texts and
+    for every text its ``k`` hardest negative images under sample-ID labels
+    (:class:`TopK` each).  The contract is symmetric, so the text side is the
+    same op with the operands and the id vectors exchanged and
+    ``−diag_offset``."""
+    i2t = pair_topk_ids(zimg, ztxt, k, img_ids, txt_ids, duplicates,
+                        diag_offset, impl=impl)
+    t2i = pair_topk_ids(ztxt, zimg, k, txt_ids, img_ids, duplicates,
+                        None if diag_offset is None else -int(diag_offset),
+                        impl=impl)
+    return i2t, t2i
+
+
+def distributed_retrieval_topk_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
+                                   k: int, image_ids: torch.Tensor,
+                                   text_ids: torch.Tensor,
+                                   duplicates: str = "positive", group=None,
+                                   impl: str = "auto"):
+    """:func:`retrieval_topk_ids` of this rank's ``b`` images against all
+    ``W·b`` texts and of its ``b`` texts against all ``W·b`` images, with
+    global indices (equal ``b`` on every rank; with ``"ignore"`` the positive
+    of local image ``i`` is local text ``i``).
+
+    The text shard and the text ids are all-gathered for the image side, the
+    image shard and the image ids for the text side; each side is one
+    :func:`pair_topk_ids` pass over a ``(b, W·b)`` block with ``diag_offset =
+    rank·b`` and complete on its own, so nothing is reduced.  World size 1 is
+    :func:`retrieval_topk_ids`."""
+    if (not dist.is_available() or not dist.is_initialized()
+            or dist.get_world_size(group) == 1):
+        return retrieval_topk_ids(zimg, ztxt, k, image_ids, text_ids,
+                                  duplicates, 0, impl=impl)
+    from .id_labels import _ids_vector
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    b = zimg.shape[0]
+    if ztxt.shape[0] != b:
+        raise RuntimeError(
+            "distributed_retrieval_topk_ids needs paired shards")
+    image_ids = _ids_vector("image_ids", image_ids, b, zimg.device)
+    text_ids = _ids_vector("text_ids", text_ids, b, zimg.device)
+
+    def gathered(z, ids):
+        ids_all = torch.empty(world * b, device=ids.device, dtype=ids.dtype)
+        dist.all_gather_into_tensor(ids_all, ids, group=group)
+        return all_gather_with_grad(z.detach(), group), ids_all
+
+    with torch.no_grad():
+        zt_all, tids_all = gathered(ztxt, text_ids)
+        i2t = pair_topk_ids(zimg.detach(), zt_all, k, image_ids, tids_all,
+                            duplicates, rank * b, impl=impl)
+        del zt_all
+        zi_all, iids_all = gathered(zimg, image_ids)
+        t2i = pair_topk_ids(ztxt.detach(), zi_all, k, text_ids, iids_all,
+                            duplicates, rank * b, impl=impl)
+    return i2t, t2i

@@ -52,6 +52,12 @@ exposes:
   tiles whose ids hold no positive — and :func:`pair_rank_counts_ids` — the
   threshold counts over the negatives only (``losses/retrieval.py`` builds
   the multi-positive ranks and their distributed form on them).
+- sample-ID labels for the top-k: :func:`pair_topk_ids` — the ``k`` best
+  scoring NEGATIVES of every row under the id labels (other captions of the
+  same image, repeated samples and padding are no candidates), the class
+  predicate turned into per-lane bit masks before each tile's dot products
+  (``losses/retrieval.py`` adds both directions, chunk merging and the
+  distributed form).
 
 Host structure: every tile-kernel launch goes through :func:`_launch_tile`,
 the only caller of the extension's single ``siglip_tile`` entry point; every
@@ -210,6 +216,9 @@ _EXPORTS = {
     # (stream, zimg, ztxt, row_thr, col_thr, img_ids, txt_ids, row_cnt,
     #  col_cnt, b, n, d, diag, mode)
     "pair_rank_counts_ids_bf16": [_P] * 9 + [_I] * 5,
+    # (stream, zimg, ztxt, img_ids, txt_ids, ws_s, ws_c, out_s, out_c, b, n,
+    #  d, diag, k, n_splits)
+    "pair_topk_ids_bf16": [_P] * 9 + [_I] * 6,
 }
 
 
@@ -1393,6 +1402,51 @@ def pair_rank_counts_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
         _DUPLICATES[duplicates]),
         "pair_rank_counts_ids_bf16")
     return row_cnt, col_cnt
+
+
+def pair_topk_ids(zimg: torch.Tensor, ztxt: torch.Tensor, k: int,
+                  img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                  duplicates: str = "positive",
+                  diag_offset: Optional[int] = None,
+                  n_splits: Optional[int] = None):
+    """:func:`pair_topk` over the negatives of sample-ID labels →
+    ``(scores (b, k) fp32, columns (b, k) int32)``.
+
+    The candidates of row ``i`` are the pairs that are neither masked nor
+    positive (the pair classes of :func:`sigmoid_ids`): both ids ``≥ 0`` and
+    different, and with ``duplicates="ignore"`` also ``j ≠ i + diag_offset``
+    (``diag_offset`` is read in that mode only).  Order, ``(−inf, −1)`` fill,
+    ``k`` range, ``n_splits`` and workspaces are those of :func:`pair_topk`; a
+    masked row is all fill.  Ids are contiguous int64 ``(b,)`` / ``(n,)`` on
+    the embeddings' device and are compared as 64-bit values.  No atomics, no
+    host sync, bitwise reproducible, no autograd."""
+    zi, zt, b, n, d, dev = _pair_block("pair_topk_ids", zimg, ztxt)
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
+    lib = _require_lib()
+    k = int(k)
+    if not 1 <= k <= lib.pair_topk_max_k():
+        raise RuntimeError(
+            f"pair_topk_ids serves 1 <= k <= {lib.pair_topk_max_k()} (got "
+            f"{k}); pass impl='torch' for more")
+    tile = lib.pair_topk_tile_dim()
+    tiles_m, tiles_n = -(-b // tile), -(-n // tile)
+    if n_splits is None:
+        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+        n_splits = -(-2 * n_cu // tiles_m)
+    n_splits = max(1, min(int(n_splits), tiles_n))
+    cap = lib.pair_topk_capacity(k)
+    ws_s = torch.empty((n_splits, b, cap), device=dev, dtype=torch.float32)
+    ws_c = torch.empty((n_splits, b, cap), device=dev, dtype=torch.int32)
+    out_s = torch.empty((b, k), device=dev, dtype=torch.float32)
+    out_c = torch.empty((b, k), device=dev, dtype=torch.int32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.pair_topk_ids_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(img_ids),
+        _ptr(txt_ids), _ptr(ws_s), _ptr(ws_c), _ptr(out_s), _ptr(out_c), b, n,
+        d, _diag_arg(diag_offset if duplicates == "ignore" else None), k,
+        n_splits),
+        "pair_topk_ids_bf16")
+    return out_s, out_c
 
 
 class PairLseIds(NamedTuple):

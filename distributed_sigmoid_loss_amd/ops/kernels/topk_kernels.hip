@@ -21,9 +21,13 @@
 //   text fragment first; the epilogue below folds it into a running sorted
 //   list of KCAP (score, column) pairs per row.  After the last tile the
 //   lists go to a workspace laid out (n_splits, b, KCAP).
-// - pair_topk_merge_kernel<KCAP>: one thread per row folds the row's n_splits
-//   workspace lists, in split order, into one list under the same total order
-//   and writes its first k entries, the (−inf, −1) fill included.
+// - pair_topk_merge_kernel<KCAP> (topk_list.h): one thread per row folds the
+//   row's n_splits workspace lists, in split order, into one list under the
+//   same total order and writes its first k entries, the (−inf, −1) fill
+//   included.
+//
+// The list, the fold, the capacities and the merge are topk_list.h's, shared
+// with topk_id_kernels.hip; this file keeps the positional candidate test.
 //
 // Tile.  pair_tile.h's, text fragment first: lane l owns image row (l & 15)
 // and the four consecutive columns 4·(l >> 4) … +3 of each fragment.
@@ -54,55 +58,9 @@
 // tile-row l / n_splits and split l % n_splits: the splits of a tile-row sit
 // on one XCD and share its image panel in L2.
 
-#include "pair_tile.h"
+#include "topk_list.h"
 
 namespace {
-
-constexpr int MAX_K = 16;        // largest compiled list capacity
-
-// Candidate buffer: [128][128] fp32 at a pitch of 129, so that the fold's
-// reads (one thread per row, often the same column) fall on distinct banks.
-// It overlays the staging buffers and needs 512 bytes more than they do.
-constexpr int CAND_PITCH = BN + 1;
-constexpr int LDS_BYTES = BM * CAND_PITCH * 4;
-
-static_assert(LDS_BYTES >= 2 * BUF_BYTES, "staging buffers exceed the LDS");
-
-// A row's running list, best first.  All indices are compile-time constants
-// after unrolling, so the list stays in registers.
-template <int KCAP>
-struct TopList {
-  float s[KCAP];
-  int c[KCAP];
-
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int q = 0; q < KCAP; ++q) {
-      s[q] = -__builtin_inff();
-      c[q] = -1;
-    }
-  }
-
-  // `col` is larger than every column already in the list: the new entry
-  // belongs behind every entry that scores at least as high.
-  __device__ __forceinline__ void insert(float v, int col) {
-    if (!(v > s[KCAP - 1])) return;
-    s[KCAP - 1] = v;
-    c[KCAP - 1] = col;
-#pragma unroll
-    for (int q = KCAP - 2; q >= 0; --q) {
-      const bool up = s[q + 1] > s[q];
-      const float hs = up ? s[q + 1] : s[q], ls = up ? s[q] : s[q + 1];
-      const int hc = up ? c[q + 1] : c[q], lc = up ? c[q] : c[q + 1];
-      s[q] = hs; s[q + 1] = ls;
-      c[q] = hc; c[q + 1] = lc;
-    }
-  }
-};
-
-__device__ __forceinline__ unsigned nib(unsigned x, int sh) {
-  return (x >> sh) & 0xfu;
-}
 
 template <int KCAP>
 __launch_bounds__(NTHREADS) __global__ void pair_topk_partials_kernel(
@@ -176,29 +134,7 @@ __launch_bounds__(NTHREADS) __global__ void pair_topk_partials_kernel(
 
     // Fold: thread `row` takes its candidates in ascending column order.
     if (tid < BM) {
-      const uint4 hv = *reinterpret_cast<const uint4*>(mask + tid * 8);
-#pragma unroll
-      for (int w = 0; w < 2; ++w) {
-        // lo: lane groups 0 (low half) and 1, hi: groups 2 and 3.
-        const unsigned lo = w ? hv.z : hv.x, hi = w ? hv.w : hv.y;
-#pragma unroll
-        for (int jp = 0; jp < 2; ++jp) {
-          // Bit jj·16 + fq·4 + r of m: fragment 2·jp + jj of wave column w.
-          unsigned m = 0;
-#pragma unroll
-          for (int jj = 0; jj < 2; ++jj) {
-            const int sh = 8 * jp + 4 * jj;
-            m |= (nib(lo, sh) | (nib(lo, 16 + sh) << 4) | (nib(hi, sh) << 8) |
-                  (nib(hi, 16 + sh) << 12)) << (16 * jj);
-          }
-          const int base = w * 64 + jp * 32;
-          while (m != 0) {
-            const int lcol = base + __builtin_ctz(m);
-            m &= m - 1;
-            top.insert(cand[tid * CAND_PITCH + lcol], n0 + lcol);
-          }
-        }
-      }
+      fold_row_candidates(top, mask, cand, tid, n0);
       thr[tid] = top.s[KCAP - 1];
     }
     // Orders the fold's reads before the next tile's staging stores, and the
@@ -216,45 +152,6 @@ __launch_bounds__(NTHREADS) __global__ void pair_topk_partials_kernel(
   }
 }
 
-// One thread per row: fold the row's n_splits lists, split 0 first, into one
-// list with the partials kernel's insert.  Its precondition holds: spans are
-// ascending column ranges and each list is sorted, so every entry arrives
-// after all entries with a lower column that score the same.
-template <int KCAP>
-__launch_bounds__(NTHREADS) __global__ void pair_topk_merge_kernel(
-    const float* __restrict__ ws_s, const int* __restrict__ ws_c,
-    float* __restrict__ out_s, int* __restrict__ out_c, int b, int k,
-    int n_splits) {
-  const long long row = (long long)blockIdx.x * NTHREADS + threadIdx.x;
-  if (row >= b) return;
-  TopList<KCAP> top;
-  top.clear();
-  for (int sp = 0; sp < n_splits; ++sp) {
-    const long long o = ((long long)sp * b + row) * KCAP;
-    float s[KCAP];
-    int c[KCAP];
-#pragma unroll
-    for (int e = 0; e < KCAP; ++e) {
-      s[e] = ws_s[o + e];
-      c[e] = ws_c[o + e];
-    }
-#pragma unroll
-    for (int e = 0; e < KCAP; ++e)
-      if (c[e] >= 0) top.insert(s[e], c[e]);   // c < 0: fill
-  }
-#pragma unroll
-  for (int q = 0; q < KCAP; ++q)
-    if (q < k) {
-      out_s[row * k + q] = top.s[q];
-      out_c[row * k + q] = top.c[q];
-    }
-}
-
-int capacity_for(int k) {
-  if (k < 1 || k > MAX_K) return 0;
-  return k <= 1 ? 1 : k <= 4 ? 4 : k <= 8 ? 8 : 16;
-}
-
 template <int KCAP>
 int launch(hipStream_t stream, const void* zimg, const void* ztxt, void* ws_s,
            void* ws_c, void* out_s, void* out_c, int b, int n, int d, int diag,
@@ -265,12 +162,7 @@ int launch(hipStream_t stream, const void* zimg, const void* ztxt, void* ws_s,
                      (int*)ws_c, b, n, d, diag, tiles_m, tiles_n, n_splits);
   const int rc = (int)hipGetLastError();
   if (rc != 0) return rc;
-  hipLaunchKernelGGL(pair_topk_merge_kernel<KCAP>,
-                     dim3((unsigned)((b + NTHREADS - 1) / NTHREADS)),
-                     dim3(NTHREADS), 0, stream, (const float*)ws_s,
-                     (const int*)ws_c, (float*)out_s, (int*)out_c, b, k,
-                     n_splits);
-  return (int)hipGetLastError();
+  return launch_merge<KCAP>(stream, ws_s, ws_c, out_s, out_c, b, k, n_splits);
 }
 
 }  // namespace
@@ -297,17 +189,11 @@ int pair_topk_capacity(int k) { return capacity_for(k); }
 int pair_topk_bf16(uintptr_t stream, const void* zimg, const void* ztxt,
                    void* ws_s, void* ws_c, void* out_s, void* out_c, int b,
                    int n, int d, int diag, int k, int n_splits) {
-  if (!pair_dims_ok(zimg, ztxt, b, n, d) || ws_s == nullptr ||
-      ws_c == nullptr || out_s == nullptr || out_c == nullptr)
-    return (int)hipErrorInvalidValue;
   const int kcap = capacity_for(k);
-  if (kcap == 0) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)ws_s | (uintptr_t)ws_c | (uintptr_t)out_s |
-       (uintptr_t)out_c) % 4 != 0)
+  if (!pair_dims_ok(zimg, ztxt, b, n, d) || kcap == 0)
     return (int)hipErrorInvalidValue;
   const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
-  if (n_splits < 1 || n_splits > tiles_n ||
-      !pair_grid_ok(tiles_m, n_splits))
+  if (!topk_args_ok(ws_s, ws_c, out_s, out_c, tiles_m, tiles_n, n_splits))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
 #define TOPK_LAUNCH(KCAP)                                                     \

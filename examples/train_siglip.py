@@ -33,7 +33,9 @@ texts, and the sample ids (global sample index // C) tell the loss that all
 ``C`` pairs of an image are positives.  Needs ``--loss sigmoid --strategy
 all_gather --quant bf16``.  ``--eval-every`` then reports the ranks under the
 same ids (``distributed_retrieval_ranks_ids``): the other captions of an
-image no longer count against it.  ``--hard-negatives`` stays positional.
+image no longer count against it.  ``--hard-negatives`` mines under the ids
+too (``distributed_retrieval_topk_ids``): the other captions of an image are
+its positives and are not returned as hard negatives.
 """
 
 from __future__ import annotations
@@ -54,6 +56,7 @@ from distributed_sigmoid_loss_amd import (
     distributed_retrieval_ranks,
     distributed_retrieval_ranks_ids,
     distributed_retrieval_topk,
+    distributed_retrieval_topk_ids,
     positive_scores,
     recall_at_k,
 )
@@ -189,9 +192,16 @@ def main():
             if args.hard_negatives > 0:
                 # Collective as well.  Every rank's margins cover its shard
                 # against the global batch; their mean is averaged over ranks.
-                neg_i2t, neg_t2i = distributed_retrieval_topk(
-                    zi.detach(), zt.detach(), args.hard_negatives,
-                    exclude_positive=True)
+                # With ids the candidates are the ids' negatives; the pair
+                # (i, i) stays a true positive under them.
+                neg_i2t, neg_t2i = (
+                    distributed_retrieval_topk(
+                        zi.detach(), zt.detach(), args.hard_negatives,
+                        exclude_positive=True)
+                    if ids is None else
+                    distributed_retrieval_topk_ids(
+                        zi.detach(), zt.detach(), args.hard_negatives, ids,
+                        ids))
                 pos = positive_scores(zi.detach(), zt.detach(), 0).float()
                 margins = torch.stack([
                     (pos - neg.scores.float().mean(1)).mean()

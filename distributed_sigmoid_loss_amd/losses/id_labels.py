@@ -42,6 +42,15 @@ tile, never building the logits, in one of two regimes:
   column chunk; the backward re-runs the kernel per band through
   ``ops.band_grad_gemms``.
 
+``quant="mixed"`` (GPU path only) keeps all of that — exact bf16 logits, the
+same loss, ``dt'`` and ``dbias`` bit for bit — and runs the two gradient GEMMs
+in fp8: ``ops.sigmoid_ids_e4m3`` writes dL/dlogit as an e4m3 slab pair (``g``
+and ``gᵀ``, ``448·g``; together the bytes of the bf16 slab), the embeddings
+are quantised per tensor (``ops.quantize_fp8_pair``) and ``ops.grad_gemms``
+takes the hipBLASLt fp8 route where every GEMM dimension is 16-aligned, the
+dequantise route otherwise.  Only ``dzimg`` and ``dztxt`` carry fp8 error.
+e4m3 *operands* for the logits (``quant="fp8"``) are not built.
+
 Per-tile partials are summed in fp64 on the device; nothing syncs with the
 host.  Elsewhere a differentiable torch composite with the same contract runs
 (fp32 compute, fp64 for fp64 inputs) — the CPU path and the tests' reference.
@@ -57,6 +66,7 @@ import torch.nn.functional as F
 from .. import ops
 
 _DUPLICATES = ("positive", "ignore")
+_QUANTS = ("bf16", "mixed")
 
 
 def pair_classes(img_ids: torch.Tensor, txt_ids: torch.Tensor,
@@ -107,23 +117,25 @@ def _torch_loss_ids(zimg, ztxt, t_prime, bias, img_ids, txt_ids, duplicates,
 
 
 class _FusedIdLoss(torch.autograd.Function):
-    """GPU path: ``ops.sigmoid_ids`` plus the library gradient GEMMs, in the
-    saved-g or the band-recompute regime (module docstring)."""
+    """GPU path: ``ops.sigmoid_ids`` (``mixed``: ``ops.sigmoid_ids_e4m3``)
+    plus the library gradient GEMMs, in the saved-g or the band-recompute
+    regime (module docstring)."""
 
     @staticmethod
     def forward(ctx, zimg, ztxt, t_prime, bias, img_ids, txt_ids, duplicates,
-                diag_offset, col_chunk, want_grad):
+                diag_offset, col_chunk, want_grad, quant):
         zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
         b, n = zimg.shape[0], ztxt.shape[0]
         # want_grad comes from the caller (grad mode is off in here).
         save_g = want_grad and col_chunk is None and b * n * 2 < 2 ** 32
         if save_g:
-            partials, g = ops.sigmoid_ids(
-                zimg, ztxt, t_prime, bias, img_ids, txt_ids, duplicates,
-                diag_offset)
+            emit = ops.sigmoid_ids_e4m3 if quant == "mixed" else ops.sigmoid_ids
+            # (partials, g) or, mixed, (partials, g8, gt8)
+            partials, *slabs = emit(zimg, ztxt, t_prime, bias, img_ids,
+                                    txt_ids, duplicates, diag_offset)
             sums = partials.double().sum(dim=0)
             ctx.save_for_backward(zimg, ztxt, t_prime, bias, img_ids,
-                                  txt_ids, sums, g)
+                                  txt_ids, sums, *slabs)
             loss = sums[0]
         else:
             step = min(n, int(col_chunk) if col_chunk and col_chunk > 0
@@ -138,7 +150,7 @@ class _FusedIdLoss(torch.autograd.Function):
             ctx.save_for_backward(zimg, ztxt, t_prime, bias, img_ids,
                                   txt_ids)
             ctx.step = step
-        ctx.save_g = save_g
+        ctx.save_g, ctx.mixed = save_g, quant == "mixed"
         ctx.duplicates, ctx.diag_offset = duplicates, diag_offset
         return loss.float()
 
@@ -148,24 +160,32 @@ class _FusedIdLoss(torch.autograd.Function):
         n, dev = ztxt.shape[0], zimg.device
         go = ops._go_scalar(grad_output, dev)
         t = ops._prep_scalar(t_prime, dev).exp()
+        # mixed: one per-tensor quantisation of the embeddings for both GEMMs.
+        qc = ops.quantize_fp8_pair(zimg, ztxt) if ctx.mixed else None
         if ctx.save_g:
-            sums, g = ctx.saved_tensors[6:]
+            sums, g, *gt = ctx.saved_tensors[6:]
             # bf16_scale=True: the products stay bf16 (see ops.grad_gemms).
-            dzimg, dztxt = ops.grad_gemms(ops.GBand(g, None, ztxt), zimg, n,
-                                          go * t, bf16_scale=True)
+            dzimg, dztxt = ops.grad_gemms(
+                ops.GBand(g, gt[0] if gt else None, ztxt, qc), zimg, n,
+                go * t, bf16_scale=True)
         else:
             parts = []
 
             def emit(j0, j1, diag_j, g, gt):
-                partials, _ = ops.sigmoid_ids(
-                    zimg, ztxt[j0:j1], t_prime, bias, img_ids,
-                    txt_ids[j0:j1], ctx.duplicates, diag_j, g=g)
+                band = (zimg, ztxt[j0:j1], t_prime, bias, img_ids,
+                        txt_ids[j0:j1], ctx.duplicates, diag_j)
+                if ctx.mixed:
+                    partials = ops.sigmoid_ids_e4m3(*band, g=g, gt=gt)[0]
+                else:
+                    partials = ops.sigmoid_ids(*band, g=g)[0]
                 parts.append(partials.double().sum(dim=0))
 
             # bf16_scale stays False, also when one band covers the block.
             dzimg, dztxt = ops.band_grad_gemms(
                 zimg, ztxt, ctx.step, emit, go * t,
-                diag_offset=ctx.diag_offset)
+                diag_offset=ctx.diag_offset,
+                g_dtype=torch.float8_e4m3fn if ctx.mixed else torch.bfloat16,
+                with_gt=ctx.mixed, qc=qc)
             sums = torch.stack(parts).sum(dim=0)
         dt = sums[1] * (go * t).double()
         db = sums[2] * go.double()
@@ -173,7 +193,7 @@ class _FusedIdLoss(torch.autograd.Function):
                 dt.to(device=t_prime.device,
                       dtype=t_prime.dtype).reshape(t_prime.shape),
                 db.to(device=bias.device, dtype=bias.dtype).reshape(bias.shape),
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
 def _ids_vector(name: str, ids, length: int, device) -> torch.Tensor:
@@ -193,7 +213,8 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
                                  duplicates: str = "positive",
                                  diag_offset: Optional[int] = None,
                                  col_chunk: Optional[int] = None,
-                                 impl: str = "auto") -> torch.Tensor:
+                                 impl: str = "auto",
+                                 quant: str = "bf16") -> torch.Tensor:
     """Sum of per-pair sigmoid cross-entropy over the ``(b, n)`` block with
     the labels taken from sample ids (see the module docstring).
     Differentiable in ``zimg``, ``ztxt``, ``t_prime`` and ``bias``.
@@ -217,6 +238,11 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
         impl: ``auto`` (``hip`` on GPU for bf16, ``torch`` elsewhere) |
             ``hip`` (bf16 on GPU, ``d % 8 == 0``; raises without the built
             extension or for other dtypes) | ``torch``.
+        quant: ``"bf16"`` | ``"mixed"`` — exact bf16 logits, e4m3 dL/dlogit
+            slabs and fp8 gradient GEMMs on the ``hip`` path (module
+            docstring); it has no effect on the ``torch`` path, which has no
+            fp8 GEMM.  ``"fp8"`` (e4m3 logit operands) is not built and
+            raises ``ValueError``.
 
     Returns a 0-d tensor; the caller normalises.
     """
@@ -225,6 +251,12 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
             f"shape mismatch: zimg {tuple(zimg.shape)} ztxt {tuple(ztxt.shape)}")
     if duplicates not in _DUPLICATES:
         raise ValueError(f"unknown duplicates {duplicates!r}")
+    if quant == "fp8":
+        raise ValueError(
+            "quant='fp8' is not built for sample-ID labels; use 'bf16' or "
+            "'mixed'")
+    if quant not in _QUANTS:
+        raise ValueError(f"unknown quant {quant!r}")
     if impl == "auto":
         impl = ("hip" if zimg.is_cuda and zimg.dtype == torch.bfloat16
                 and ztxt.dtype == torch.bfloat16 else "torch")
@@ -240,4 +272,5 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
     want_grad = torch.is_grad_enabled() and any(
         t.requires_grad for t in (zimg, ztxt, t_prime, bias))
     return _FusedIdLoss.apply(zimg, ztxt, t_prime, bias, img_ids, txt_ids,
-                              duplicates, diag_offset, col_chunk, want_grad)
+                              duplicates, diag_offset, col_chunk, want_grad,
+                              quant)

@@ -40,7 +40,10 @@ exposes:
   negatives and ignored pairs come from int64 id vectors (several positives
   per row, duplicates switched off, padding rows), as per-tile
   ``(loss, Σ g·s, Σ g)`` partials plus the optional dL/dlogit slab
-  (``losses/id_labels.py`` builds the loss and its two backward regimes).
+  (``losses/id_labels.py`` builds the loss and its two backward regimes);
+  :func:`sigmoid_ids_e4m3` — the same pass writing dL/dlogit as the e4m3
+  slab pair (``g`` and ``gᵀ``, ``448·g``) that :func:`grad_gemms` runs on
+  hipBLASLt fp8: the ``mixed`` policy of that loss.
 - sample-ID labels for the softmax loss: :func:`pair_lse_ids` — masked row
   and column log-sum-exp plus each row's and column's positive-logit sum and
   positive count — and :func:`softmax_g_ids` — the dL/dlogit slab with
@@ -203,6 +206,9 @@ _EXPORTS = {
     # (stream, zimg, ztxt, t', bias, img_ids, txt_ids, g, ws, b, n, d, ldg,
     #  diag, mode)
     "sigmoid_ids_bf16": [_P] * 9 + [_I] * 3 + [_L] + [_I] * 2,
+    # (stream, zimg, ztxt, t', bias, img_ids, txt_ids, g8, gt8, ws, b, n, d,
+    #  ldg, ldgt, diag, mode)
+    "sigmoid_ids_e4m3": [_P] * 10 + [_I] * 3 + [_L] * 2 + [_I] * 2,
     "softmax_ids_tile_dim": [],
     # (stream, zimg, ztxt, t', img_ids, txt_ids, row_ws, col_ws, row_lse,
     #  row_pos, row_cnt, col_lse, col_pos, col_cnt, b, n, d, diag, mode)
@@ -1018,17 +1024,20 @@ def _diag_arg(diag_offset: Optional[int]) -> int:
     return diag if -(2 ** 31) < diag < 2 ** 31 else _DIAG_NONE
 
 
-def _g_view(g: Optional[torch.Tensor], b: int, n: int, device):
-    """The dL/dlogit slab of a ``(b, n)`` block, allocated here or the
-    caller's view after validation; returns ``(g, ldg)``."""
+def _g_view(g: Optional[torch.Tensor], b: int, n: int, device,
+            dtype=torch.bfloat16, name: str = "g"):
+    """The dL/dlogit slab of a ``(b, n)`` block (``dtype`` bf16, or e4m3 for
+    a slab of the pair), allocated here or the caller's view after
+    validation; returns ``(g, ldg)``."""
     if g is None:
-        g = torch.empty((b, n), device=device, dtype=torch.bfloat16)
-    elif (g.device != device or g.dtype != torch.bfloat16
+        g = torch.empty((b, n), device=device, dtype=dtype)
+    elif (g.device != device or g.dtype != dtype
           or g.shape != (b, n) or g.stride(1) != 1
           or (b > 1 and g.stride(0) < n)):
+        kind = "bf16" if dtype == torch.bfloat16 else "float8_e4m3fn"
         raise RuntimeError(
-            f"g must be a bf16 ({b}, {n}) view with unit column stride on "
-            f"{device} (got {g.dtype} {tuple(g.shape)}, strides "
+            f"{name} must be a {kind} ({b}, {n}) view with unit column "
+            f"stride on {device} (got {g.dtype} {tuple(g.shape)}, strides "
             f"{tuple(g.stride())} on {g.device})")
     return g, max(g.stride(0), n)
 
@@ -1306,6 +1315,45 @@ def sigmoid_ids(zimg: torch.Tensor, ztxt: torch.Tensor, t_prime: torch.Tensor,
         _DUPLICATES[duplicates]),
         "sigmoid_ids_bf16")
     return partials, g
+
+
+def sigmoid_ids_e4m3(zimg: torch.Tensor, ztxt: torch.Tensor,
+                     t_prime: torch.Tensor, bias: torch.Tensor,
+                     img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                     duplicates: str = "positive",
+                     diag_offset: Optional[int] = None,
+                     g: Optional[torch.Tensor] = None,
+                     gt: Optional[torch.Tensor] = None):
+    """:func:`sigmoid_ids` with dL/dlogit as the e4m3 slab pair of the
+    ``mixed`` policy → ``(partials, g, gt)``: ``g`` ``(b, n)`` and its
+    transpose ``gt`` ``(n, b)``, both ``torch.float8_e4m3fn`` holding
+    ``448·g`` rounded to nearest even (``|g| ≤ 1``, so nothing saturates) and
+    byte ``0x00`` where the pair is masked — what :func:`grad_gemms` takes as
+    ``GBand(g, gt, ...)``.  The logits are the exact bf16 ones and
+    ``partials`` comes from the fp32 ``g``: bit for bit :func:`sigmoid_ids`'s.
+
+    Each slab is allocated here or is the caller's view with unit column
+    stride — a column band of a wider ``g``, a row band of a wider ``gᵀ`` —
+    of any alignment; only its elements are touched.  Labels, scalars and
+    every check are :func:`sigmoid_ids`'s; nothing is launched on a failure.
+    No autograd."""
+    zi, zt, b, n, d, dev = _pair_block("sigmoid_ids_e4m3", zimg, ztxt)
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
+    g, ldg = _g_view(g, b, n, dev, torch.float8_e4m3fn)
+    gt, ldgt = _g_view(gt, n, b, dev, torch.float8_e4m3fn, "gt")
+    lib = _require_lib()
+    tile = lib.sigmoid_ids_tile_dim()
+    tp, bp = _prep_scalar(t_prime, dev), _prep_scalar(bias, dev)
+    partials = torch.empty((-(-b // tile) * -(-n // tile), 3), device=dev,
+                           dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.sigmoid_ids_e4m3(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(bp),
+        _ptr(img_ids), _ptr(txt_ids), _ptr(g), _ptr(gt), _ptr(partials), b, n,
+        d, ctypes.c_longlong(ldg), ctypes.c_longlong(ldgt),
+        _diag_arg(diag_offset), _DUPLICATES[duplicates]),
+        "sigmoid_ids_e4m3")
+    return partials, g, gt
 
 
 def _best_side(name: str, on: bool, best, length: int, device):

@@ -12,14 +12,28 @@
 //   negative : everything else
 //   x = −l·z (l = ±1)   term = softplus(x)   g = −l·σ(x)      (0 where masked)
 //
-// One kernel template <WRITE_G>.  Both instantiations leave three fp32
+// One tile body template <GFMT>, three kernels.  All leave three fp32
 // partials per 128×128 tile — Σ term, Σ g·s, Σ g — in a (tiles, 3) workspace;
-// WRITE_G = true also stages the bf16 g tile in LDS and writes it as
-// coalesced 16-byte row segments into a (b, n) view of row stride ldg.
-// WRITE_G = false has no staging and no stores to g.  The partials of the
-// two are bit-identical: the arithmetic is the same sequence of explicit
-// fmas, and every reduction has a fixed order (xor shuffles, then the four
-// waves in wave order).  No atomics, no counters.
+// G_BF16 also stages the bf16 g tile in LDS and writes it as coalesced
+// 16-byte row segments into a (b, n) view of row stride ldg; G_NONE has no
+// staging and no stores to g; G_E4M3 writes g as a (b, n) e4m3 slab and gᵀ
+// as an (n, b) e4m3 slab (below).  The partials of the three are
+// bit-identical: they come from the fp32 g, the arithmetic is the same
+// sequence of explicit fmas, and every reduction has a fixed order (xor
+// shuffles, then the four waves in wave order).  No atomics, no counters.
+//
+// The e4m3 slab pair (the `mixed` policy: exact bf16 logits, fp8 gradient
+// GEMMs).  Both slabs hold the OCP e4m3fn code of 448·g, the encoding of
+// siglip_kernels.hip's pair; a masked or padding pair is byte 0x00.  A lane's
+// four values of a fragment are four consecutive bytes of one g row: one
+// packed dword, one 4-byte LDS write.  gᵀ wants four consecutive rows of one
+// column: lanes fr = 4a … 4a+3 are a DPP quad and hold a 4×4 byte block,
+// which pair_tile.h's quad_transpose_bytes turns in place (2 DPP moves, 2
+// v_perm_b32), so lane fr & 3 = c holds column 4·fq + c, rows 4a … 4a+3, and
+// does one 4-byte write into a [column][row] tile.  16 dword writes per slab
+// per lane, one staging barrier (the reduction's), two coalesced write-outs
+// (store_g8_tile).  The two tiles take 36 KiB; ids and reduction slots sit
+// above them.  This kernel is compiled without packed fp32 instructions.
 //
 // Structure.  The tile, its main loop (text fragment first: lane l owns image
 // row (l & 15) and the four consecutive text columns 4·(l >> 4) … +3 of each
@@ -42,23 +56,33 @@
 
 namespace {
 
-constexpr int IDS_OFF = G_STAGE_BYTES;        // 128 row ids, 128 column ids
-constexpr int RED_OFF = IDS_OFF + IDS_BYTES;  // 4 waves × 3 partials
+enum { G_NONE = 0, G_BF16 = 1, G_E4M3 = 2 };
 
-static_assert(IDS_OFF % 16 == 0, "id staging must take 16-byte reads");
-static_assert(RED_OFF + 64 <= 2 * BUF_BYTES, "epilogue staging exceeds LDS");
+// 128 row ids and 128 column ids above the g staging, then 4 waves × 3
+// partials.
+constexpr int ids_off(int gfmt) {
+  return gfmt == G_E4M3 ? 2 * G8_TILE_BYTES : G_STAGE_BYTES;
+}
+constexpr int red_off(int gfmt) { return ids_off(gfmt) + IDS_BYTES; }
 
-template <bool WRITE_G>
-__launch_bounds__(NTHREADS) __global__ void sigmoid_ids_kernel(
+static_assert(ids_off(G_BF16) % 16 == 0 && ids_off(G_E4M3) % 16 == 0,
+              "id staging must take 16-byte reads");
+static_assert(red_off(G_BF16) + 64 <= 2 * BUF_BYTES &&
+                  red_off(G_E4M3) + 64 <= 2 * BUF_BYTES,
+              "epilogue staging exceeds LDS");
+
+// One tile: g is the bf16 slab (G_BF16) or the e4m3 slab (G_E4M3), gt the
+// e4m3 transpose (G_E4M3 only).  `lds` is the workgroup's 2 · BUF_BYTES.
+template <int GFMT>
+__device__ __forceinline__ void sigmoid_ids_tile(
     const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt,
     const float* __restrict__ tprime, const float* __restrict__ bias,
     const long long* __restrict__ img_ids,
-    const long long* __restrict__ txt_ids, __bf16* __restrict__ g,
-    float* __restrict__ ws, int b, int n, int d, long long ldg, int diag,
-    int ignore_dups, int tiles_m, int tiles_n) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
-  static_assert(sizeof(lds) >= 2 * BUF_BYTES, "staging buffers exceed the LDS");
-
+    const long long* __restrict__ txt_ids, void* __restrict__ g,
+    void* __restrict__ gt, float* __restrict__ ws, int b, int n, int d,
+    long long ldg, long long ldgt, int diag, int ignore_dups, int tiles_m,
+    int tiles_n, unsigned char* lds) {
+  constexpr int IDS_OFF = ids_off(GFMT), RED_OFF = red_off(GFMT);
   const TilePos tp = tile_of_block(tiles_m, tiles_n);
   const int m0 = tp.tm * BM, n0 = tp.tn * BN;
   f32x4 acc[4][4];
@@ -97,6 +121,7 @@ __launch_bounds__(NTHREADS) __global__ void sigmoid_ids_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       bf16x4 out;
+      f32x4 gq;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float s = acc[i][j][r];
@@ -120,11 +145,22 @@ __launch_bounds__(NTHREADS) __global__ void sigmoid_ids_kernel(
         s_loss += term;
         s_gs = __builtin_fmaf(gv, s, s_gs);
         s_g += gv;
-        if (WRITE_G) out[r] = (__bf16)gv;
+        if (GFMT == G_BF16) out[r] = (__bf16)gv;
+        if (GFMT == G_E4M3) gq[r] = gv;
       }
-      if (WRITE_G)
+      if (GFMT == G_BF16)
         *reinterpret_cast<bf16x4*>(lds + (wm * 64 + i * 16 + fr) * G_PITCH
                                    + 2 * lcol0) = out;
+      if (GFMT == G_E4M3) {
+        // g: row fr, columns lcol0 … +3.  gᵀ after the quad transpose:
+        // column lcol0 + (fr & 3), rows 4·(fr >> 2) … +3 of this fragment.
+        const unsigned codes = pack_e4m3x4(gq);
+        *reinterpret_cast<unsigned*>(lds + (wm * 64 + i * 16 + fr) * G8_PITCH
+                                     + lcol0) = codes;
+        *reinterpret_cast<unsigned*>(
+            lds + G8_TILE_BYTES + (lcol0 + (fr & 3)) * G8_PITCH + wm * 64 +
+            i * 16 + (fr & 12)) = quad_transpose_bytes(codes, fr & 3);
+      }
     }
   }
 
@@ -147,9 +183,40 @@ __launch_bounds__(NTHREADS) __global__ void sigmoid_ids_kernel(
     ws[((long long)tp.tm * tiles_n + tp.tn) * 3 + tid] =
         ((red[tid] + red[3 + tid]) + red[6 + tid]) + red[9 + tid];
 
-  if (!WRITE_G) return;
+  if (GFMT == G_BF16) store_g_tile(lds, (__bf16*)g, ldg, m0, n0, b, n);
+  if (GFMT == G_E4M3) {
+    store_g8_tile(lds, (unsigned char*)g, ldg, m0, n0, b, n);
+    store_g8_tile(lds + G8_TILE_BYTES, (unsigned char*)gt, ldgt, n0, m0, n, b);
+  }
+}
 
-  store_g_tile(lds, g, ldg, m0, n0, b, n);
+template <bool WRITE_G>
+__launch_bounds__(NTHREADS) __global__ void sigmoid_ids_kernel(
+    const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt,
+    const float* __restrict__ tprime, const float* __restrict__ bias,
+    const long long* __restrict__ img_ids,
+    const long long* __restrict__ txt_ids, __bf16* __restrict__ g,
+    float* __restrict__ ws, int b, int n, int d, long long ldg, int diag,
+    int ignore_dups, int tiles_m, int tiles_n) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
+  sigmoid_ids_tile<WRITE_G ? G_BF16 : G_NONE>(
+      zimg, ztxt, tprime, bias, img_ids, txt_ids, g, nullptr, ws, b, n, d, ldg,
+      0, diag, ignore_dups, tiles_m, tiles_n, lds);
+}
+
+__attribute__((target("no-packed-fp32-ops")))
+__launch_bounds__(NTHREADS) __global__ void sigmoid_ids_e4m3_kernel(
+    const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt,
+    const float* __restrict__ tprime, const float* __restrict__ bias,
+    const long long* __restrict__ img_ids,
+    const long long* __restrict__ txt_ids, unsigned char* __restrict__ g8,
+    unsigned char* __restrict__ gt8, float* __restrict__ ws, int b, int n,
+    int d, long long ldg, long long ldgt, int diag, int ignore_dups,
+    int tiles_m, int tiles_n) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
+  sigmoid_ids_tile<G_E4M3>(zimg, ztxt, tprime, bias, img_ids, txt_ids, g8, gt8,
+                           ws, b, n, d, ldg, ldgt, diag, ignore_dups, tiles_m,
+                           tiles_n, lds);
 }
 
 }  // namespace
@@ -200,6 +267,37 @@ int sigmoid_ids_bf16(uintptr_t stream, const void* zimg, const void* ztxt,
                        (const long long*)txt_ids, (__bf16*)nullptr,
                        (float*)ws, b, n, d, ldg, diag, mode, tiles_m,
                        tiles_n);
+  return (int)hipGetLastError();
+}
+
+// The same loss with dL/dlogit as an e4m3 slab pair: g8 a (b, n) view of row
+// stride ldg bytes, gt8 an (n, b) view of row stride ldgt bytes, both the
+// e4m3fn code of 448·g (0x00 where masked), any alignment.  Everything else,
+// and ws bit for bit, as sigmoid_ids_bf16.  Returns non-zero, launching
+// nothing, on anything unsupported.
+int sigmoid_ids_e4m3(uintptr_t stream, const void* zimg, const void* ztxt,
+                     const void* tprime, const void* bias,
+                     const void* img_ids, const void* txt_ids, void* g8,
+                     void* gt8, void* ws, int b, int n, int d, long long ldg,
+                     long long ldgt, int diag, int mode) {
+  if (!pair_dims_ok(zimg, ztxt, b, n, d) || tprime == nullptr ||
+      bias == nullptr || img_ids == nullptr || txt_ids == nullptr ||
+      ws == nullptr || g8 == nullptr || gt8 == nullptr ||
+      (mode != 0 && mode != 1))
+    return (int)hipErrorInvalidValue;
+  if (((uintptr_t)img_ids | (uintptr_t)txt_ids) % 8 != 0 ||
+      ((uintptr_t)tprime | (uintptr_t)bias | (uintptr_t)ws) % 4 != 0)
+    return (int)hipErrorInvalidValue;
+  if (ldg < n || ldgt < b) return (int)hipErrorInvalidValue;
+  const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
+  if (!pair_grid_ok(tiles_m, tiles_n)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(sigmoid_ids_e4m3_kernel, dim3(tiles_m * tiles_n),
+                     dim3(NTHREADS), 0, (hipStream_t)stream,
+                     (const __bf16*)zimg, (const __bf16*)ztxt,
+                     (const float*)tprime, (const float*)bias,
+                     (const long long*)img_ids, (const long long*)txt_ids,
+                     (unsigned char*)g8, (unsigned char*)gt8, (float*)ws, b, n,
+                     d, ldg, ldgt, diag, mode, tiles_m, tiles_n);
   return (int)hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 // rank_id_kernels.hip (gfx950, MI355X): constants, the block walk, the main
 // loop that leaves a tile of <zimg_i, ztxt_j> dot products in MFMA
 // accumulators, and the helpers the epilogues share (the positive's column,
-// the log-sum-exp guard, the sample-id staging, the g write-out).  Each
+// the log-sum-exp guard, the sample-id staging, the g write-out in bf16 and
+// as an e4m3 slab pair).  Each
 // including file adds its own epilogue and C entry points; nothing here is
 // exported.  Everything sits in an anonymous namespace, so each translation
 // unit gets its own copy.
@@ -298,6 +299,73 @@ __device__ __forceinline__ void store_g_tile(const unsigned char* lds,
 #pragma unroll
       for (int x = 0; x < 8; ++x)
         if (col + x < n) dst16[x] = h[x];
+    }
+  }
+}
+
+// The e4m3 slab pair (g and gᵀ, one byte per pair): two staging tiles of
+// [128][G8_PITCH] bytes.  144 B = 36 dwords: the 4-byte writes of lanes (row
+// or column index q = 0..15, dword a = 0..3) fall on banks 36·q + a, all 64
+// distinct, and rows r and r + 8 start 32 banks apart, which is what
+// store_g8_tile's 16-byte reads use.
+constexpr int G8_PITCH = BN + 16;
+constexpr int G8_TILE_BYTES = BM * G8_PITCH;  // 18 KiB each
+
+// Four values of |v| ≤ 1 as OCP e4m3fn codes of 448·v (round to nearest
+// even, saturating), v[0] in the low byte: what __hip_fp8_e4m3(448·v) gives
+// for each, two at a time.  0 gives 0x00.
+__device__ __forceinline__ unsigned pack_e4m3x4(f32x4 v) {
+  float a[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    a[r] = __builtin_amdgcn_fmed3f(v[r] * 448.0f, 448.0f, -448.0f);
+  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a[0], a[1], 0, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(a[2], a[3], w, true);
+  return (unsigned)w;
+}
+
+// 4×4 byte transpose inside a DPP quad (four adjacent lanes): lane c holds
+// row c as one dword, byte k = column k; on return it holds column c, byte
+// r = row r.  Two quad-permute moves (lane ^ 2, lane ^ 1) and two byte
+// selects: 16-bit halves first, then bytes.  Every lane of the quad must be
+// active.
+__device__ __forceinline__ unsigned quad_transpose_bytes(unsigned x, int c) {
+  unsigned y = (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xf, 0xf, true);
+  x = __builtin_amdgcn_perm(y, x, (c & 2) ? 0x03020706u : 0x05040100u);
+  y = (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xf, 0xf, true);
+  return __builtin_amdgcn_perm(y, x, (c & 1) ? 0x03070105u : 0x06020400u);
+}
+
+// Write-out of one byte tile staged at `tile` ([128] rows at G8_PITCH bytes)
+// into the (rows, cols) byte view `dst` of row stride ld, tile origin
+// (r0, c0): 8 threads cover one 128-byte tile row, and a 16-lane group reads
+// rows r and r + 8 (distinct banks).  A 16-byte store where the segment is
+// whole and its address aligned, byte stores otherwise (ragged edge, odd row
+// stride or offset); only elements of the view are touched.  g: rows are
+// image rows; gᵀ: rows are text rows.  The caller's barrier orders the
+// staging writes before this.
+__device__ __forceinline__ void store_g8_tile(const unsigned char* tile,
+                                              unsigned char* __restrict__ dst,
+                                              long long ld, int r0, int c0,
+                                              int rows, int cols) {
+  const int tid = threadIdx.x;
+  const int ch = tid & 7;
+  const int lrow0 = ((tid >> 4) & 7) + 8 * ((tid >> 3) & 1) + 16 * (tid >> 7);
+#pragma unroll
+  for (int k = 0; k < BM / 32; ++k) {
+    const int lrow = lrow0 + 32 * k;
+    const int row = r0 + lrow, col = c0 + ch * 16;
+    if (row >= rows || col >= cols) continue;
+    const uint4 v =
+        *reinterpret_cast<const uint4*>(tile + lrow * G8_PITCH + 16 * ch);
+    unsigned char* p = dst + (long long)row * ld + col;
+    if (col + 16 <= cols && ((uintptr_t)p & 15) == 0) {
+      *reinterpret_cast<uint4*>(p) = v;
+    } else {
+      const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int x = 0; x < 16; ++x)
+        if (col + x < cols) p[x] = (unsigned char)(w[x >> 2] >> (8 * (x & 3)));
     }
   }
 }

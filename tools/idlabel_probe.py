@@ -3,6 +3,7 @@ kernel at the same shape and against the stock composite it replaces, in one
 process.
 
     python tools/idlabel_probe.py [--batch 32768 8192] [--dim 768] [--iters 30]
+                                  [--quant bf16|mixed] [--only all|loss|g|g8]
 
 At each (B, B, d) bf16 shape, L2-normalised inputs, ``t = 10``, ``bias =
 −10``; ids uniform over ``B // 3`` values (each id appears 3 times on average)
@@ -18,9 +19,18 @@ max) of ``--iters`` warm calls timed one by one between device events:
                ``t·zi @ zt.T + bias``, labels from ``ids[:, None] ==
                ids[None, :]``, a masked ``F.logsigmoid``, ``backward()``.
 
+``--quant mixed`` is a row set of its own for the ``mixed`` policy, each pair
+timed alternately in this process, with the shipped fp8 GEMM table loaded
+(``ops.load_tuned_gemms()``, as the module does for ``mixed``):
+
+- ``g8`` against ``g``: ``ops.sigmoid_ids_e4m3`` writing the e4m3 slab pair
+  against the bf16 g-writing kernel;
+- ``mixed`` against ``bf16``: fused forward + backward with ``quant="mixed"``
+  against ``quant="bf16"``, and the peak memory of each.
+
 ``fused`` and ``stock`` are timed alternately, call by call, so that drift of
 the clocks hits both alike.  Peak memory of each is the growth of
-``torch.cuda.max_memory_allocated`` over one call.  ``--only loss|g`` times
+``torch.cuda.max_memory_allocated`` over one call.  ``--only loss|g|g8`` times
 one kernel alone (for a kernel-trace run).  Prints one JSON line per shape.
 """
 
@@ -83,7 +93,7 @@ def peak_mib(fn):
     return round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1)
 
 
-def probe(b, d, iters, only):
+def probe(b, d, iters, only, quant="bf16"):
     gen = torch.Generator(device="cuda").manual_seed(0)
     zi = F.normalize(torch.randn(b, d, device="cuda", generator=gen),
                      dim=-1).bfloat16()
@@ -106,6 +116,9 @@ def probe(b, d, iters, only):
         out.update({f"{name}_ms": stats[0], f"{name}_min_ms": stats[1],
                     f"{name}_max_ms": stats[2]})
 
+    if quant == "mixed" or only == "g8":
+        return probe_mixed(out, zi, zt, tp, bias, img_ids, txt_ids, iters,
+                           only)
     if only in ("all", "loss"):
         put("loss", median_ms(lambda: ops.sigmoid_ids(
             zi, zt, tp, bias, img_ids, txt_ids, want_g=False), iters))
@@ -153,20 +166,67 @@ def probe(b, d, iters, only):
     return out
 
 
+def probe_mixed(out, zi, zt, tp, bias, img_ids, txt_ids, iters, only):
+    b = zi.shape[0]
+    out["quant"] = "mixed"
+    out["tuned_gemms"] = ops.load_tuned_gemms()
+
+    def put(name, stats):
+        out.update({f"{name}_ms": stats[0], f"{name}_min_ms": stats[1],
+                    f"{name}_max_ms": stats[2]})
+
+    g8 = torch.empty((b, b), device="cuda", dtype=torch.float8_e4m3fn)
+    gt8 = torch.empty((b, b), device="cuda", dtype=torch.float8_e4m3fn)
+
+    def run_g8():
+        ops.sigmoid_ids_e4m3(zi, zt, tp, bias, img_ids, txt_ids, g=g8, gt=gt8)
+
+    if only == "g8":
+        put("g8", median_ms(run_g8, iters))
+        return out
+    g_buf = torch.empty((b, b), device="cuda", dtype=torch.bfloat16)
+    g8_stats, g_stats = alternate_ms(run_g8, lambda: ops.sigmoid_ids(
+        zi, zt, tp, bias, img_ids, txt_ids, g=g_buf), iters)
+    put("g8", g8_stats)
+    put("g", g_stats)
+    out["g8_over_g"] = round(out["g8_ms"] / out["g_ms"], 3)
+    del g8, gt8, g_buf
+
+    leaves = [x.clone().requires_grad_() for x in (zi, zt, tp, bias)]
+
+    def step(quant):
+        def run():
+            for x in leaves:
+                x.grad = None
+            sigmoid_contrastive_loss_ids(*leaves, img_ids, txt_ids,
+                                         impl="hip", quant=quant).backward()
+        return run
+
+    m_stats, b_stats = alternate_ms(step("mixed"), step("bf16"), iters)
+    put("mixed", m_stats)
+    put("bf16", b_stats)
+    out["bf16_over_mixed"] = round(out["bf16_ms"] / out["mixed_ms"], 3)
+    out["mixed_peak_mib"] = peak_mib(step("mixed"))
+    out["bf16_peak_mib"] = peak_mib(step("bf16"))
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, nargs="+", default=[32768, 8192])
     p.add_argument("--dim", type=int, default=768)
     p.add_argument("--iters", type=int, default=30)
-    p.add_argument("--only", choices=["all", "loss", "g"], default="all")
+    p.add_argument("--only", choices=["all", "loss", "g", "g8"],
+                   default="all")
+    p.add_argument("--quant", choices=["bf16", "mixed"], default="bf16")
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("idlabel_probe needs a GPU")
     if args.iters < 20:
         raise SystemExit("--iters must be at least 20")
     for b in args.batch:
-        print(json.dumps(probe(b, args.dim, args.iters, args.only)),
-              flush=True)
+        print(json.dumps(probe(b, args.dim, args.iters, args.only,
+                               args.quant)), flush=True)
         torch.cuda.empty_cache()
 
 

@@ -49,7 +49,18 @@ and ``gᵀ``, ``448·g``; together the bytes of the bf16 slab), the embeddings
 are quantised per tensor (``ops.quantize_fp8_pair``) and ``ops.grad_gemms``
 takes the hipBLASLt fp8 route where every GEMM dimension is 16-aligned, the
 dequantise route otherwise.  Only ``dzimg`` and ``dztxt`` carry fp8 error.
-e4m3 *operands* for the logits (``quant="fp8"``) are not built.
+
+``quant="fp8"`` (GPU path only) runs the logits on e4m3 operands as well: the
+embeddings are quantised once per step (``ops.quantize_fp8_pair``; the cache
+travels to the backward), ``ops.sigmoid_ids_fp8`` reads the e4m3 pair on the
+MX-scaled MFMA with unit block scales — the per-tensor scales are added to
+``t'`` on the device, ``t' + log s_img + log s_txt`` — and writes the same
+e4m3 slab pair, or nothing in the loss-only form the band regime and
+forwards without gradients use.  The backward is the ``mixed`` one, straight
+through the quantisation; ``dt' = exp(t' + log s_img + log s_txt)·Σ g·s`` with
+``s`` the raw e4m3 dot.  Loss, ``dt'`` and ``dbias`` are those of the
+quantised embeddings, not the bf16 path's bits.  Not built: per-row (e8m0)
+scales, and ids under ``fp8`` / ``mixed`` in ``DistributedSigmoidLoss``.
 
 Per-tile partials are summed in fp64 on the device; nothing syncs with the
 host.  Elsewhere a differentiable torch composite with the same contract runs
@@ -66,7 +77,7 @@ import torch.nn.functional as F
 from .. import ops
 
 _DUPLICATES = ("positive", "ignore")
-_QUANTS = ("bf16", "mixed")
+_QUANTS = ("bf16", "mixed", "fp8")
 
 
 def pair_classes(img_ids: torch.Tensor, txt_ids: torch.Tensor,
@@ -117,54 +128,84 @@ def _torch_loss_ids(zimg, ztxt, t_prime, bias, img_ids, txt_ids, duplicates,
 
 
 class _FusedIdLoss(torch.autograd.Function):
-    """GPU path: ``ops.sigmoid_ids`` (``mixed``: ``ops.sigmoid_ids_e4m3``)
-    plus the library gradient GEMMs, in the saved-g or the band-recompute
-    regime (module docstring)."""
+    """GPU path: ``ops.sigmoid_ids`` (``mixed``: ``ops.sigmoid_ids_e4m3``;
+    ``fp8``: ``ops.sigmoid_ids_fp8`` on the quantised pair) plus the library
+    gradient GEMMs, in the saved-g or the band-recompute regime (module
+    docstring)."""
 
     @staticmethod
     def forward(ctx, zimg, ztxt, t_prime, bias, img_ids, txt_ids, duplicates,
                 diag_offset, col_chunk, want_grad, quant):
         zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
         b, n = zimg.shape[0], ztxt.shape[0]
+        fp8 = quant == "fp8"
+        zi_k, zt_k, tp_k, qts = zimg, ztxt, t_prime, ()
+        if fp8:
+            # One quantisation per step; the kernel reads the e4m3 pair with
+            # unit scales and the per-tensor scales ride on the temperature.
+            ops._validate(zimg, ztxt, "fp8")
+            qc = ops.quantize_fp8_pair(zimg, ztxt)
+            zi_k, zt_k, qts = qc.zi_q, qc.zt_q, qc.tensors()
+            tp_k = (ops._prep_scalar(t_prime, zimg.device) + qc.si.log()
+                    + qc.st.log())
         # want_grad comes from the caller (grad mode is off in here).
         save_g = want_grad and col_chunk is None and b * n * 2 < 2 ** 32
         if save_g:
-            emit = ops.sigmoid_ids_e4m3 if quant == "mixed" else ops.sigmoid_ids
-            # (partials, g) or, mixed, (partials, g8, gt8)
-            partials, *slabs = emit(zimg, ztxt, t_prime, bias, img_ids,
-                                    txt_ids, duplicates, diag_offset)
+            emit = {"bf16": ops.sigmoid_ids, "mixed": ops.sigmoid_ids_e4m3,
+                    "fp8": ops.sigmoid_ids_fp8}[quant]
+            # (partials, g) or, mixed and fp8, (partials, g8, gt8)
+            partials, *slabs = emit(zi_k, zt_k, tp_k, bias, img_ids, txt_ids,
+                                    duplicates, diag_offset)
             sums = partials.double().sum(dim=0)
             ctx.save_for_backward(zimg, ztxt, t_prime, bias, img_ids,
-                                  txt_ids, sums, *slabs)
+                                  txt_ids, *qts, sums, *slabs)
             loss = sums[0]
         else:
             step = min(n, int(col_chunk) if col_chunk and col_chunk > 0
                        else ops.banded_col_step(b))
+            loss_only = ops.sigmoid_ids_fp8 if fp8 else ops.sigmoid_ids
             loss = torch.zeros((), device=zimg.device, dtype=torch.float64)
             for j0, j1, diag_j in ops.col_bands(n, step, diag_offset):
-                partials, _ = ops.sigmoid_ids(
-                    zimg, ztxt[j0:j1], t_prime, bias, img_ids,
-                    txt_ids[j0:j1], duplicates, diag_j, want_g=False)
+                partials = loss_only(
+                    zi_k, zt_k[j0:j1], tp_k, bias, img_ids,
+                    txt_ids[j0:j1], duplicates, diag_j, want_g=False)[0]
                 # the same reduction as saved-g: one block gives the same bits
                 loss = loss + partials.double().sum(dim=0)[0]
             ctx.save_for_backward(zimg, ztxt, t_prime, bias, img_ids,
-                                  txt_ids)
+                                  txt_ids, *qts)
             ctx.step = step
-        ctx.save_g, ctx.mixed = save_g, quant == "mixed"
+        ctx.save_g, ctx.quant, ctx.n_q = save_g, quant, len(qts)
         ctx.duplicates, ctx.diag_offset = duplicates, diag_offset
         return loss.float()
 
     @staticmethod
     def backward(ctx, grad_output):
         zimg, ztxt, t_prime, bias, img_ids, txt_ids = ctx.saved_tensors[:6]
+        rest = ctx.saved_tensors[6 + ctx.n_q:]
         n, dev = ztxt.shape[0], zimg.device
+        fp8, fp8_gemms = ctx.quant == "fp8", ctx.quant != "bf16"
         go = ops._go_scalar(grad_output, dev)
         t = ops._prep_scalar(t_prime, dev).exp()
-        # mixed: one per-tensor quantisation of the embeddings for both GEMMs.
-        qc = ops.quantize_fp8_pair(zimg, ztxt) if ctx.mixed else None
+        # mixed: one per-tensor quantisation of the embeddings for both GEMMs;
+        # fp8: the forward's.
+        qc = None
+        if fp8:
+            qc = ops.QuantCache.from_tensors(ctx.saved_tensors[6:6 + ctx.n_q])
+        elif fp8_gemms:
+            qc = ops.quantize_fp8_pair(zimg, ztxt)
+        # The kernel's t' and what multiplies its Σ g·s in dt': under fp8 the
+        # dot is of e4m3 values, so the per-tensor scales come back in here
+        # (the forward's expression, for the forward's bits).
+        tp_k, t_k = t_prime, t
+        if fp8:
+            tp_k = (ops._prep_scalar(t_prime, dev) + qc.si.log()
+                    + qc.st.log())
+            t_k = tp_k.exp()
         if ctx.save_g:
-            sums, g, *gt = ctx.saved_tensors[6:]
+            sums, g, *gt = rest
             # bf16_scale=True: the products stay bf16 (see ops.grad_gemms).
+            # The GEMMs see the true temperature and, off the fp8 route, the
+            # bf16 embeddings: straight-through w.r.t. the quantisation.
             dzimg, dztxt = ops.grad_gemms(
                 ops.GBand(g, gt[0] if gt else None, ztxt, qc), zimg, n,
                 go * t, bf16_scale=True)
@@ -172,22 +213,27 @@ class _FusedIdLoss(torch.autograd.Function):
             parts = []
 
             def emit(j0, j1, diag_j, g, gt):
-                band = (zimg, ztxt[j0:j1], t_prime, bias, img_ids,
-                        txt_ids[j0:j1], ctx.duplicates, diag_j)
-                if ctx.mixed:
-                    partials = ops.sigmoid_ids_e4m3(*band, g=g, gt=gt)[0]
+                labels = (bias, img_ids, txt_ids[j0:j1], ctx.duplicates,
+                          diag_j)
+                if fp8:
+                    partials = ops.sigmoid_ids_fp8(
+                        qc.zi_q, qc.zt_q[j0:j1], tp_k, *labels, g=g, gt=gt)[0]
+                elif fp8_gemms:
+                    partials = ops.sigmoid_ids_e4m3(
+                        zimg, ztxt[j0:j1], tp_k, *labels, g=g, gt=gt)[0]
                 else:
-                    partials = ops.sigmoid_ids(*band, g=g)[0]
+                    partials = ops.sigmoid_ids(
+                        zimg, ztxt[j0:j1], tp_k, *labels, g=g)[0]
                 parts.append(partials.double().sum(dim=0))
 
             # bf16_scale stays False, also when one band covers the block.
             dzimg, dztxt = ops.band_grad_gemms(
                 zimg, ztxt, ctx.step, emit, go * t,
                 diag_offset=ctx.diag_offset,
-                g_dtype=torch.float8_e4m3fn if ctx.mixed else torch.bfloat16,
-                with_gt=ctx.mixed, qc=qc)
+                g_dtype=torch.float8_e4m3fn if fp8_gemms else torch.bfloat16,
+                with_gt=fp8_gemms, qc=qc)
             sums = torch.stack(parts).sum(dim=0)
-        dt = sums[1] * (go * t).double()
+        dt = sums[1] * (go * t_k).double()
         db = sums[2] * go.double()
         return (dzimg, dztxt,
                 dt.to(device=t_prime.device,
@@ -241,8 +287,9 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
         quant: ``"bf16"`` | ``"mixed"`` — exact bf16 logits, e4m3 dL/dlogit
             slabs and fp8 gradient GEMMs on the ``hip`` path (module
             docstring); it has no effect on the ``torch`` path, which has no
-            fp8 GEMM.  ``"fp8"`` (e4m3 logit operands) is not built and
-            raises ``ValueError``.
+            fp8 GEMM.  ``"fp8"`` — e4m3 logit operands as well, ``hip`` path
+            only (``d % 16 == 0``); with the ``torch`` path, which has no
+            e4m3 logits, it raises ``ValueError``.
 
     Returns a 0-d tensor; the caller normalises.
     """
@@ -251,10 +298,6 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
             f"shape mismatch: zimg {tuple(zimg.shape)} ztxt {tuple(ztxt.shape)}")
     if duplicates not in _DUPLICATES:
         raise ValueError(f"unknown duplicates {duplicates!r}")
-    if quant == "fp8":
-        raise ValueError(
-            "quant='fp8' is not built for sample-ID labels; use 'bf16' or "
-            "'mixed'")
     if quant not in _QUANTS:
         raise ValueError(f"unknown quant {quant!r}")
     if impl == "auto":
@@ -262,6 +305,11 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
                 and ztxt.dtype == torch.bfloat16 else "torch")
     if impl not in ("hip", "torch"):
         raise ValueError(f"unknown impl {impl!r}")
+    if quant == "fp8" and impl == "torch":
+        # no e4m3 logits here, and bf16-policy values would be a silent lie
+        raise ValueError(
+            "quant='fp8' needs the hip path (bf16 embeddings on a GPU); the "
+            "torch path has no e4m3 logits")
     img_ids = _ids_vector("img_ids", img_ids, zimg.shape[0], zimg.device)
     txt_ids = _ids_vector("txt_ids", txt_ids, ztxt.shape[0], zimg.device)
     if duplicates != "ignore":

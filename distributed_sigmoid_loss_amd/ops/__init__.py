@@ -43,7 +43,9 @@ exposes:
   (``losses/id_labels.py`` builds the loss and its two backward regimes);
   :func:`sigmoid_ids_e4m3` — the same pass writing dL/dlogit as the e4m3
   slab pair (``g`` and ``gᵀ``, ``448·g``) that :func:`grad_gemms` runs on
-  hipBLASLt fp8: the ``mixed`` policy of that loss.
+  hipBLASLt fp8: the ``mixed`` policy of that loss; :func:`sigmoid_ids_fp8`
+  — the pass from e4m3 operands on the MX-scaled MFMA (the pair tile's e4m3
+  main loop), loss only or writing the same slab pair: the ``fp8`` policy.
 - sample-ID labels for the softmax loss: :func:`pair_lse_ids` — masked row
   and column log-sum-exp plus each row's and column's positive-logit sum and
   positive count — and :func:`softmax_g_ids` — the dL/dlogit slab with
@@ -209,6 +211,9 @@ _EXPORTS = {
     # (stream, zimg, ztxt, t', bias, img_ids, txt_ids, g8, gt8, ws, b, n, d,
     #  ldg, ldgt, diag, mode)
     "sigmoid_ids_e4m3": [_P] * 10 + [_I] * 3 + [_L] * 2 + [_I] * 2,
+    # (stream, zimg_q, ztxt_q, t', bias, img_ids, txt_ids, g8, gt8, ws, b, n,
+    #  d, ldg, ldgt, diag, mode)
+    "sigmoid_ids_fp8": [_P] * 10 + [_I] * 3 + [_L] * 2 + [_I] * 2,
     "softmax_ids_tile_dim": [],
     # (stream, zimg, ztxt, t', img_ids, txt_ids, row_ws, col_ws, row_lse,
     #  row_pos, row_cnt, col_lse, col_pos, col_cnt, b, n, d, diag, mode)
@@ -1353,6 +1358,76 @@ def sigmoid_ids_e4m3(zimg: torch.Tensor, ztxt: torch.Tensor,
         d, ctypes.c_longlong(ldg), ctypes.c_longlong(ldgt),
         _diag_arg(diag_offset), _DUPLICATES[duplicates]),
         "sigmoid_ids_e4m3")
+    return partials, g, gt
+
+
+def sigmoid_ids_fp8(zimg_q: torch.Tensor, ztxt_q: torch.Tensor,
+                    t_prime: torch.Tensor, bias: torch.Tensor,
+                    img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                    duplicates: str = "positive",
+                    diag_offset: Optional[int] = None,
+                    g: Optional[torch.Tensor] = None,
+                    gt: Optional[torch.Tensor] = None, want_g: bool = True):
+    """:func:`sigmoid_ids` from e4m3 operands on the MX-scaled MFMA — the
+    ``fp8`` policy of that loss → ``(partials, g | None, gt | None)``.
+
+    ``zimg_q`` ``(b, d)`` and ``ztxt_q`` ``(n, d)`` are contiguous
+    ``torch.float8_e4m3fn`` on one GPU, ``d % 16 == 0``
+    (:func:`quantize_fp8_pair`'s ``zi_q`` / ``zt_q``).  The kernel runs with
+    unit block scales: ``s`` is the raw dot of the e4m3 values and ``z =
+    exp(t_prime)·s + bias``, so the caller folds its per-tensor scales into
+    ``t_prime`` (``t' + log si + log st``); ``partials`` — ``Σ softplus(−l·z)``,
+    ``Σ g·s``, ``Σ g`` per tile — is in those units.
+
+    ``want_g=False`` runs the loss-only kernel.  Otherwise the e4m3 slab pair
+    of :func:`sigmoid_ids_e4m3` is written — the same encoding (``448·g``,
+    ``0x00`` where masked), the same views — both slabs allocated here or both
+    the caller's; ``partials`` is the loss-only kernel's bit for bit.  Labels
+    and scalars as :func:`sigmoid_ids`; every failure raises before any
+    launch.  No autograd."""
+    E4M3 = torch.float8_e4m3fn
+    for what, x in (("zimg_q", zimg_q), ("ztxt_q", ztxt_q)):
+        if (not isinstance(x, torch.Tensor) or x.dim() != 2
+                or x.dtype != E4M3 or not x.is_cuda
+                or not x.is_contiguous()):
+            raise RuntimeError(
+                f"sigmoid_ids_fp8: {what} must be a contiguous float8_e4m3fn "
+                f"2-D GPU tensor (got {getattr(x, 'dtype', type(x))} "
+                f"{tuple(getattr(x, 'shape', ()))} on "
+                f"{getattr(x, 'device', None)})")
+    if zimg_q.shape[1] != ztxt_q.shape[1] or ztxt_q.device != zimg_q.device:
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings on one device, got "
+            f"{tuple(zimg_q.shape)} and {tuple(ztxt_q.shape)}")
+    (b, d), n, dev = zimg_q.shape, ztxt_q.shape[0], zimg_q.device
+    if b < 1 or n < 1:
+        raise RuntimeError("sigmoid_ids_fp8 needs a non-empty block")
+    if d % 16 != 0:
+        raise RuntimeError(
+            f"emb dim must be a multiple of 16 for fp8 (got {d})")
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
+    ldg, ldgt = n, b
+    if not want_g:
+        if g is not None or gt is not None:
+            raise RuntimeError("g / gt given with want_g=False")
+    elif (g is None) != (gt is None):
+        raise RuntimeError("g and gt must be given together (or neither)")
+    else:
+        g, ldg = _g_view(g, b, n, dev, E4M3)
+        gt, ldgt = _g_view(gt, n, b, dev, E4M3, "gt")
+    lib = _require_lib()
+    tile = lib.sigmoid_ids_tile_dim()
+    tp, bp = _prep_scalar(t_prime, dev), _prep_scalar(bias, dev)
+    partials = torch.empty((-(-b // tile) * -(-n // tile), 3), device=dev,
+                           dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.sigmoid_ids_fp8(
+        ctypes.c_void_p(stream), _ptr(zimg_q), _ptr(ztxt_q), _ptr(tp),
+        _ptr(bp), _ptr(img_ids), _ptr(txt_ids), _ptr(g), _ptr(gt),
+        _ptr(partials), b, n, d, ctypes.c_longlong(ldg),
+        ctypes.c_longlong(ldgt), _diag_arg(diag_offset),
+        _DUPLICATES[duplicates]),
+        "sigmoid_ids_fp8")
     return partials, g, gt
 
 

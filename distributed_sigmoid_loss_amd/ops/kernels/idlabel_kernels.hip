@@ -12,7 +12,8 @@
 //   negative : everything else
 //   x = −l·z (l = ±1)   term = softplus(x)   g = −l·σ(x)      (0 where masked)
 //
-// One tile body template <GFMT>, three kernels.  All leave three fp32
+// One tile body template <GFMT, OP>, three kernels on bf16 operands (two
+// more on e4m3 operands, below).  All leave three fp32
 // partials per 128×128 tile — Σ term, Σ g·s, Σ g — in a (tiles, 3) workspace;
 // G_BF16 also stages the bf16 g tile in LDS and writes it as coalesced
 // 16-byte row segments into a (b, n) view of row stride ldg; G_NONE has no
@@ -34,6 +35,16 @@
 // per lane, one staging barrier (the reduction's), two coalesced write-outs
 // (store_g8_tile).  The two tiles take 36 KiB; ids and reduction slots sit
 // above them.  This kernel is compiled without packed fp32 instructions.
+//
+// e4m3 operands (the `fp8` policy).  The tile body takes the operand type as
+// a second template parameter and calls pair_tile.h's e4m3 main loop
+// (v_mfma_scale_f32_16x16x128_f8f6f4, unit block scales, half the K steps)
+// instead of the bf16 one; everything after the K loop is the same code.  Two
+// more kernels, sigmoid_ids_fp8_kernel<false> (G_NONE) and <true> (G_E4M3),
+// both without packed fp32 instructions, so their partials agree bit for bit
+// with each other (not with the bf16-operand kernels: other logits).  s is
+// the raw dot of the e4m3 values and the per-tensor scales arrive folded into
+// t'; row-wise scales are not built.
 //
 // Structure.  The tile, its main loop (text fragment first: lane l owns image
 // row (l & 15) and the four consecutive text columns 4·(l >> 4) … +3 of each
@@ -72,10 +83,12 @@ static_assert(red_off(G_BF16) + 64 <= 2 * BUF_BYTES &&
               "epilogue staging exceeds LDS");
 
 // One tile: g is the bf16 slab (G_BF16) or the e4m3 slab (G_E4M3), gt the
-// e4m3 transpose (G_E4M3 only).  `lds` is the workgroup's 2 · BUF_BYTES.
-template <int GFMT>
+// e4m3 transpose (G_E4M3 only).  OP is the operand element: __bf16, or
+// unsigned char for e4m3 (s is then the raw dot of the e4m3 values and
+// tprime holds the folded scales).  `lds` is the workgroup's 2 · BUF_BYTES.
+template <int GFMT, typename OP = __bf16>
 __device__ __forceinline__ void sigmoid_ids_tile(
-    const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt,
+    const OP* __restrict__ zimg, const OP* __restrict__ ztxt,
     const float* __restrict__ tprime, const float* __restrict__ bias,
     const long long* __restrict__ img_ids,
     const long long* __restrict__ txt_ids, void* __restrict__ g,
@@ -86,7 +99,10 @@ __device__ __forceinline__ void sigmoid_ids_tile(
   const TilePos tp = tile_of_block(tiles_m, tiles_n);
   const int m0 = tp.tm * BM, n0 = tp.tn * BN;
   f32x4 acc[4][4];
-  pair_tile_dots<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
+  if constexpr (sizeof(OP) == 1)
+    pair_tile_dots_e4m3<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
+  else
+    pair_tile_dots<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -219,6 +235,26 @@ __launch_bounds__(NTHREADS) __global__ void sigmoid_ids_e4m3_kernel(
                            tiles_n, lds);
 }
 
+// e4m3 operands (the `fp8` policy): loss only (WRITE_G false; g8, gt8 unused)
+// or the e4m3 slab pair.  Compiled without packed fp32 instructions, both, so
+// that the two leave the same partials.
+template <bool WRITE_G>
+__attribute__((target("no-packed-fp32-ops")))
+__launch_bounds__(NTHREADS) __global__ void sigmoid_ids_fp8_kernel(
+    const unsigned char* __restrict__ zimg_q,
+    const unsigned char* __restrict__ ztxt_q,
+    const float* __restrict__ tprime, const float* __restrict__ bias,
+    const long long* __restrict__ img_ids,
+    const long long* __restrict__ txt_ids, unsigned char* __restrict__ g8,
+    unsigned char* __restrict__ gt8, float* __restrict__ ws, int b, int n,
+    int d, long long ldg, long long ldgt, int diag, int ignore_dups,
+    int tiles_m, int tiles_n) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
+  sigmoid_ids_tile<WRITE_G ? G_E4M3 : G_NONE, unsigned char>(
+      zimg_q, ztxt_q, tprime, bias, img_ids, txt_ids, g8, gt8, ws, b, n, d,
+      ldg, ldgt, diag, ignore_dups, tiles_m, tiles_n, lds);
+}
+
 }  // namespace
 
 extern "C" {
@@ -298,6 +334,41 @@ int sigmoid_ids_e4m3(uintptr_t stream, const void* zimg, const void* ztxt,
                      (const long long*)img_ids, (const long long*)txt_ids,
                      (unsigned char*)g8, (unsigned char*)gt8, (float*)ws, b, n,
                      d, ldg, ldgt, diag, mode, tiles_m, tiles_n);
+  return (int)hipGetLastError();
+}
+
+// The loss from e4m3 operands: zimg_q (b, d), ztxt_q (n, d) OCP e4m3fn bytes,
+// row-major contiguous, d a multiple of 16.  s is the raw dot of the e4m3
+// values and z = exp(*tprime)·s + bias, so the caller adds the logs of its
+// per-tensor scales to t'; ws[tile] = (Σ term, Σ g·s, Σ g) in those units.
+// g8 and gt8 both null: loss only; both given: the slab pair of
+// sigmoid_ids_e4m3 (same views, same encoding); exactly one: an error.
+// Returns non-zero, launching nothing, on anything unsupported.
+int sigmoid_ids_fp8(uintptr_t stream, const void* zimg_q, const void* ztxt_q,
+                    const void* tprime, const void* bias, const void* img_ids,
+                    const void* txt_ids, void* g8, void* gt8, void* ws, int b,
+                    int n, int d, long long ldg, long long ldgt, int diag,
+                    int mode) {
+  if (!pair_dims_ok_e4m3(zimg_q, ztxt_q, b, n, d) || tprime == nullptr ||
+      bias == nullptr || img_ids == nullptr || txt_ids == nullptr ||
+      ws == nullptr || (g8 == nullptr) != (gt8 == nullptr) ||
+      (mode != 0 && mode != 1))
+    return (int)hipErrorInvalidValue;
+  if (((uintptr_t)img_ids | (uintptr_t)txt_ids) % 8 != 0 ||
+      ((uintptr_t)tprime | (uintptr_t)bias | (uintptr_t)ws) % 4 != 0)
+    return (int)hipErrorInvalidValue;
+  if (g8 != nullptr && (ldg < n || ldgt < b)) return (int)hipErrorInvalidValue;
+  const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
+  if (!pair_grid_ok(tiles_m, tiles_n)) return (int)hipErrorInvalidValue;
+  const auto kernel = g8 != nullptr ? sigmoid_ids_fp8_kernel<true>
+                                    : sigmoid_ids_fp8_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(tiles_m * tiles_n), dim3(NTHREADS), 0,
+                     (hipStream_t)stream, (const unsigned char*)zimg_q,
+                     (const unsigned char*)ztxt_q, (const float*)tprime,
+                     (const float*)bias, (const long long*)img_ids,
+                     (const long long*)txt_ids, (unsigned char*)g8,
+                     (unsigned char*)gt8, (float*)ws, b, n, d, ldg, ldgt, diag,
+                     mode, tiles_m, tiles_n);
   return (int)hipGetLastError();
 }
 

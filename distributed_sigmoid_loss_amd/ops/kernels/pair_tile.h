@@ -20,6 +20,23 @@
 // 256-byte bank row.  Two workgroups (64 KiB each) share a CU and hide each
 // other's staging.
 //
+// e4m3 operands (pair_tile_dots_e4m3; idlabel_kernels.hip is its first user).
+// The same tile, waves and accumulator layouts with one byte per element: a
+// k-step is 128 elements, so the slab is byte for byte the bf16 one —
+// [128 rows][128 B] per operand, the same staging thread map, lds_off and
+// swizzle — and a step carries twice the k for the same bytes moved, the same
+// LDS traffic and one barrier.  A fragment is one
+// v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales (per-tensor scales
+// are the caller's, folded into its temperature): lane l supplies row l & 15
+// and the 32-byte K-block l >> 4, chunks 2·(l >> 4) and 2·(l >> 4) + 1 of its
+// row, two ds_read_b128.  Each of the two reads takes one fixed chunk index
+// over the 16 rows of a fragment, which is the bf16 read pattern: the XOR with
+// (row >> 1) & 7 gives 8 distinct slots over the 8 row pairs and the row
+// parity picks the 128-byte half, 16 distinct 16-byte slots of the 256-byte
+// bank row.  A fragment is 8 VGPRs, so the loop keeps the four text fragments
+// of a step and streams the image fragments one at a time (40 VGPRs of
+// fragments, not 64).
+//
 // Placement.  One workgroup per tile on a 1-D grid; the block id is remapped
 // so consecutive logical ids share an XCD, and logical ids walk the tile grid
 // in groups of 8 tile-rows, column by column, so the workgroups in flight on
@@ -36,6 +53,7 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(8))) int i32x8;
 
 constexpr int BM = 128;          // image rows per tile
 constexpr int BN = 128;          // text rows (logit columns) per tile
@@ -64,6 +82,15 @@ inline bool pair_dims_ok(const void* zimg, const void* ztxt, int b, int n,
   if (zimg == nullptr || ztxt == nullptr) return false;
   if (b < 1 || n < 1 || d < 8 || d % 8 != 0) return false;
   return ((uintptr_t)zimg | (uintptr_t)ztxt) % 16 == 0;
+}
+
+// The same for e4m3 embeddings (one byte per element): d a positive multiple
+// of 16, so that a row is a whole number of aligned 16-byte chunks.
+inline bool pair_dims_ok_e4m3(const void* zimg_q, const void* ztxt_q, int b,
+                              int n, int d) {
+  if (zimg_q == nullptr || ztxt_q == nullptr) return false;
+  if (b < 1 || n < 1 || d < 16 || d % 16 != 0) return false;
+  return ((uintptr_t)zimg_q | (uintptr_t)ztxt_q) % 16 == 0;
 }
 
 // A 1-D grid of rows · cols workgroups stays below 2³¹ (the block walk is in
@@ -211,6 +238,126 @@ __device__ __forceinline__ void pair_tile_dots(
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
               TEXT_FIRST ? bfr[j] : af[i], TEXT_FIRST ? af[i] : bfr[j],
               acc[i][j], 0, 0, 0);
+    }
+
+    if (more) store_step((s + 1) & 1);
+    __syncthreads();
+  }
+}
+
+// The main loop for e4m3 operands: zimg_q (b, d) and ztxt_q (n, d) are OCP
+// e4m3fn bytes, row-major contiguous, d % 16 == 0 (pair_dims_ok_e4m3).  The
+// contract of pair_tile_dots: the same acc layouts for both values of
+// TEXT_FIRST, rows past b / n and k past d zero-filled (byte 0x00 is +0),
+// 64-bit byte offsets, the same `lds`, and it ends on a barrier.  acc holds
+// the raw dots of the e4m3 values: the MFMA runs with unit block scales and
+// the caller folds its per-tensor scales into what it multiplies the dot by.
+//
+// A k-step is BK8 = 128 elements, one 128-byte LDS row, so staging is the
+// bf16 code with 16 elements per chunk.  Per step a lane reads chunks 2·fq and
+// 2·fq + 1 of its fragment row (the K-block the MFMA takes from lane group
+// fq; both operands use the same map, so every product pairs equal k), keeps
+// the four text fragments and streams the image fragments: 16 MFMAs of
+// 16×16×128 per wave and step against 32 of 16×16×32 per 64 k for bf16.
+constexpr int BK8 = ROW_BYTES;   // e4m3 k per step: one 128-byte LDS row
+constexpr int MX_UNIT_SCALE = 0x7f7f7f7f;   // e8m0 127 = 2⁰ in every byte
+
+template <bool TEXT_FIRST>
+__device__ __forceinline__ void pair_tile_dots_e4m3(
+    const unsigned char* __restrict__ zimg_q,
+    const unsigned char* __restrict__ ztxt_q, int b, int n, int d, int m0,
+    int n0, unsigned char* lds, f32x4 (&acc)[4][4]) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+
+  // Staging: thread t owns chunk t&7 of rows (t>>3) + 32·i, i = 0..3.
+  const int ld_ch = tid & 7;
+  const int ld_row = tid >> 3;
+  const unsigned char* a_src[LOADS];
+  const unsigned char* b_src[LOADS];
+  bool a_ok[LOADS], b_ok[LOADS];
+  int st_off[LOADS];
+#pragma unroll
+  for (int i = 0; i < LOADS; ++i) {
+    const int row = ld_row + 32 * i;
+    a_ok[i] = m0 + row < b;
+    b_ok[i] = n0 + row < n;
+    a_src[i] = zimg_q + (long long)(m0 + row) * d + ld_ch * 16;
+    b_src[i] = ztxt_q + (long long)(n0 + row) * d + ld_ch * 16;
+    st_off[i] = lds_off(row, ld_ch);
+  }
+
+  // Fragment reads: lane l takes row (l & 15), k = 32·(l >> 4) … +31 of the
+  // 128-deep MFMA step, i.e. chunks 2·(l >> 4) and 2·(l >> 4) + 1.
+  const int fr = lane & 15, fq = lane >> 4;
+  int a_off[4][2], b_off[4][2];
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      a_off[f][h] = lds_off(wm * 64 + f * 16 + fr, 2 * fq + h);
+      b_off[f][h] = OP_BYTES + lds_off(wn * 64 + f * 16 + fr, 2 * fq + h);
+    }
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  uint4 ra[LOADS], rb[LOADS];
+
+  auto load_step = [&](int s) {
+    const int k0 = s * BK8;
+    const bool k_ok = k0 + ld_ch * 16 < d;    // d % 16 == 0: all or nothing
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      ra[i] = uint4{0u, 0u, 0u, 0u};
+      rb[i] = uint4{0u, 0u, 0u, 0u};
+      if (k_ok && a_ok[i])
+        ra[i] = *reinterpret_cast<const uint4*>(a_src[i] + k0);
+      if (k_ok && b_ok[i])
+        rb[i] = *reinterpret_cast<const uint4*>(b_src[i] + k0);
+    }
+  };
+  auto store_step = [&](int buf) {
+    unsigned char* base = lds + buf * BUF_BYTES;
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      *reinterpret_cast<uint4*>(base + st_off[i]) = ra[i];
+      *reinterpret_cast<uint4*>(base + OP_BYTES + st_off[i]) = rb[i];
+    }
+  };
+  auto fragment = [](const unsigned char* base, const int (&off)[2]) {
+    const uint4 lo = *reinterpret_cast<const uint4*>(base + off[0]);
+    const uint4 hi = *reinterpret_cast<const uint4*>(base + off[1]);
+    return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w,
+                 (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+  };
+
+  const int nsteps = (d + BK8 - 1) / BK8;
+  load_step(0);
+  store_step(0);
+  __syncthreads();
+
+  for (int s = 0; s < nsteps; ++s) {
+    const bool more = s + 1 < nsteps;
+    if (more) load_step(s + 1);
+
+    const unsigned char* base = lds + (s & 1) * BUF_BYTES;
+    i32x8 bfr[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) bfr[f] = fragment(base, b_off[f]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const i32x8 af = fragment(base, a_off[i]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            TEXT_FIRST ? bfr[j] : af, TEXT_FIRST ? af : bfr[j], acc[i][j],
+            0, 0,                                   // both operands e4m3
+            0, MX_UNIT_SCALE, 0, MX_UNIT_SCALE);
     }
 
     if (more) store_step((s + 1) & 1);

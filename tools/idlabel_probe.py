@@ -3,7 +3,8 @@ kernel at the same shape and against the stock composite it replaces, in one
 process.
 
     python tools/idlabel_probe.py [--batch 32768 8192] [--dim 768] [--iters 30]
-                                  [--quant bf16|mixed] [--only all|loss|g|g8]
+                                  [--quant bf16|mixed|fp8]
+                                  [--only all|loss|g|g8|loss8|pair8]
 
 At each (B, B, d) bf16 shape, L2-normalised inputs, ``t = 10``, ``bias =
 −10``; ids uniform over ``B // 3`` values (each id appears 3 times on average)
@@ -28,10 +29,21 @@ timed alternately in this process, with the shipped fp8 GEMM table loaded
 - ``mixed`` against ``bf16``: fused forward + backward with ``quant="mixed"``
   against ``quant="bf16"``, and the peak memory of each.
 
+``--quant fp8`` is the row set of the ``fp8`` policy, again in alternating
+pairs with the GEMM table loaded; the e4m3 pair is quantised once outside the
+timed calls and its scales are added to ``t'``:
+
+- ``loss8`` against ``loss``: ``ops.sigmoid_ids_fp8(want_g=False)`` against
+  the bf16 loss-only kernel;
+- ``pair8`` against ``g8``: ``ops.sigmoid_ids_fp8`` writing the slab pair
+  against ``ops.sigmoid_ids_e4m3``, into the same buffers;
+- ``fp8`` against ``mixed``: fused forward + backward, and the peak memory.
+
 ``fused`` and ``stock`` are timed alternately, call by call, so that drift of
 the clocks hits both alike.  Peak memory of each is the growth of
-``torch.cuda.max_memory_allocated`` over one call.  ``--only loss|g|g8`` times
-one kernel alone (for a kernel-trace run).  Prints one JSON line per shape.
+``torch.cuda.max_memory_allocated`` over one call.  ``--only
+loss|g|g8|loss8|pair8`` times one kernel alone (for a kernel-trace run).
+Prints one JSON line per shape.
 """
 
 import argparse
@@ -116,6 +128,8 @@ def probe(b, d, iters, only, quant="bf16"):
         out.update({f"{name}_ms": stats[0], f"{name}_min_ms": stats[1],
                     f"{name}_max_ms": stats[2]})
 
+    if quant == "fp8" or only in ("loss8", "pair8"):
+        return probe_fp8(out, zi, zt, tp, bias, img_ids, txt_ids, iters, only)
     if quant == "mixed" or only == "g8":
         return probe_mixed(out, zi, zt, tp, bias, img_ids, txt_ids, iters,
                            only)
@@ -211,14 +225,73 @@ def probe_mixed(out, zi, zt, tp, bias, img_ids, txt_ids, iters, only):
     return out
 
 
+def probe_fp8(out, zi, zt, tp, bias, img_ids, txt_ids, iters, only):
+    b = zi.shape[0]
+    out["quant"] = "fp8"
+    out["tuned_gemms"] = ops.load_tuned_gemms()
+    flop = 2.0 * b * b * zi.shape[1]
+
+    def put(name, stats):
+        out.update({f"{name}_ms": stats[0], f"{name}_min_ms": stats[1],
+                    f"{name}_max_ms": stats[2]})
+
+    qc = ops.quantize_fp8_pair(zi, zt)
+    tp8 = tp + qc.si.log() + qc.st.log()
+    ids = (bias, img_ids, txt_ids)
+    g8 = torch.empty((b, b), device="cuda", dtype=torch.float8_e4m3fn)
+    gt8 = torch.empty((b, b), device="cuda", dtype=torch.float8_e4m3fn)
+
+    def loss8():
+        ops.sigmoid_ids_fp8(qc.zi_q, qc.zt_q, tp8, *ids, want_g=False)
+
+    def pair8():
+        ops.sigmoid_ids_fp8(qc.zi_q, qc.zt_q, tp8, *ids, g=g8, gt=gt8)
+
+    if only in ("loss8", "pair8"):
+        put(only, median_ms(loss8 if only == "loss8" else pair8, iters))
+        return out
+    l8, l16 = alternate_ms(loss8, lambda: ops.sigmoid_ids(
+        zi, zt, tp, *ids, want_g=False), iters)
+    put("loss8", l8)
+    put("loss", l16)
+    out["loss8_over_loss"] = round(out["loss8_ms"] / out["loss_ms"], 3)
+    out["loss8_tflops"] = round(flop / out["loss8_ms"] * 1e-9, 1)
+    p8, p16 = alternate_ms(pair8, lambda: ops.sigmoid_ids_e4m3(
+        zi, zt, tp, *ids, g=g8, gt=gt8), iters)
+    put("pair8", p8)
+    put("g8", p16)
+    out["pair8_over_g8"] = round(out["pair8_ms"] / out["g8_ms"], 3)
+    del g8, gt8
+
+    leaves = [x.clone().requires_grad_() for x in (zi, zt, tp, bias)]
+
+    def step(quant):
+        def run():
+            for x in leaves:
+                x.grad = None
+            sigmoid_contrastive_loss_ids(*leaves, img_ids, txt_ids,
+                                         impl="hip", quant=quant).backward()
+        return run
+
+    f_stats, m_stats = alternate_ms(step("fp8"), step("mixed"), iters)
+    put("fp8", f_stats)
+    put("mixed", m_stats)
+    out["mixed_over_fp8"] = round(out["mixed_ms"] / out["fp8_ms"], 3)
+    out["fp8_peak_mib"] = peak_mib(step("fp8"))
+    out["mixed_peak_mib"] = peak_mib(step("mixed"))
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, nargs="+", default=[32768, 8192])
     p.add_argument("--dim", type=int, default=768)
     p.add_argument("--iters", type=int, default=30)
-    p.add_argument("--only", choices=["all", "loss", "g", "g8"],
+    p.add_argument("--only",
+                   choices=["all", "loss", "g", "g8", "loss8", "pair8"],
                    default="all")
-    p.add_argument("--quant", choices=["bf16", "mixed"], default="bf16")
+    p.add_argument("--quant", choices=["bf16", "mixed", "fp8"],
+                   default="bf16")
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("idlabel_probe needs a GPU")

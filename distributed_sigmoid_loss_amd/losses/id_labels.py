@@ -59,8 +59,23 @@ e4m3 slab pair, or nothing in the loss-only form the band regime and
 forwards without gradients use.  The backward is the ``mixed`` one, straight
 through the quantisation; ``dt' = exp(t' + log s_img + log s_txt)·Σ g·s`` with
 ``s`` the raw e4m3 dot.  Loss, ``dt'`` and ``dbias`` are those of the
-quantised embeddings, not the bf16 path's bits.  Not built: per-row (e8m0)
-scales, and ids under ``fp8`` / ``mixed`` in ``DistributedSigmoidLoss``.
+quantised embeddings, not the bf16 path's bits.
+
+``quant="mxfp8"`` (GPU path only, ``d % 32 == 0``) is the ``fp8`` policy with
+OCP MX block scales instead of one scale per tensor: ``ops.quantize_mx`` gives
+each operand e4m3 elements and one e8m0 scale per 32 consecutive elements of
+a row (one pass, once per step), and ``ops.sigmoid_ids_mx`` hands the scales
+to the MX-scaled MFMA, so ``s`` is the true dot of the dequantised values and
+``t'`` is passed unchanged.  A block's scale is set by its own maximum, so
+rows or blocks of very different magnitude keep e4m3's precision where one
+per-tensor scale would flush the small ones; on unit-norm rows the logits are
+as accurate as ``fp8``'s, not more (``profiles/README.md``).  Regimes as for ``fp8`` (bands slice the
+text elements, scales and ids by rows); the backward is the ``mixed`` one
+unchanged — a per-tensor ``ops.quantize_fp8_pair`` of the bf16 embeddings
+for the two gradient GEMMs — and ``dt' = exp(t')·Σ g·s``, straight through.
+
+Not built: ids under ``fp8`` / ``mixed`` / ``mxfp8`` in
+``DistributedSigmoidLoss``, and MX operands for the gradient GEMMs.
 
 Per-tile partials are summed in fp64 on the device; nothing syncs with the
 host.  Elsewhere a differentiable torch composite with the same contract runs
@@ -77,7 +92,7 @@ import torch.nn.functional as F
 from .. import ops
 
 _DUPLICATES = ("positive", "ignore")
-_QUANTS = ("bf16", "mixed", "fp8")
+_QUANTS = ("bf16", "mixed", "fp8", "mxfp8")
 
 
 def pair_classes(img_ids: torch.Tensor, txt_ids: torch.Tensor,
@@ -129,8 +144,8 @@ def _torch_loss_ids(zimg, ztxt, t_prime, bias, img_ids, txt_ids, duplicates,
 
 class _FusedIdLoss(torch.autograd.Function):
     """GPU path: ``ops.sigmoid_ids`` (``mixed``: ``ops.sigmoid_ids_e4m3``;
-    ``fp8``: ``ops.sigmoid_ids_fp8`` on the quantised pair) plus the library
-    gradient GEMMs, in the saved-g or the band-recompute regime (module
+    ``fp8``: ``ops.sigmoid_ids_fp8`` on the quantised pair; ``mxfp8``:
+    ``ops.sigmoid_ids_mx`` on the MX pair) plus the library gradient GEMMs, in the saved-g or the band-recompute regime (module
     docstring)."""
 
     @staticmethod
@@ -148,14 +163,30 @@ class _FusedIdLoss(torch.autograd.Function):
             zi_k, zt_k, qts = qc.zi_q, qc.zt_q, qc.tensors()
             tp_k = (ops._prep_scalar(t_prime, zimg.device) + qc.si.log()
                     + qc.st.log())
+        mx = quant == "mxfp8"
+        if mx:
+            # One MX quantisation per step; the block scales are applied in
+            # the kernel's dot, so t' goes in unchanged.
+            ops._validate(zimg, ztxt, "bf16")
+            if zimg.shape[1] % 32 != 0:
+                raise RuntimeError(
+                    f"emb dim must be a multiple of 32 for mxfp8 (got "
+                    f"{zimg.shape[1]})")
+            zi_q, zi_e8 = ops.quantize_mx(zimg)
+            zt_q, zt_e8 = ops.quantize_mx(ztxt)
         # want_grad comes from the caller (grad mode is off in here).
         save_g = want_grad and col_chunk is None and b * n * 2 < 2 ** 32
-        if save_g:
+        if save_g and mx:
+            partials, *slabs = ops.sigmoid_ids_mx(
+                zi_q, zi_e8, zt_q, zt_e8, t_prime, bias, img_ids, txt_ids,
+                duplicates, diag_offset)
+        elif save_g:
             emit = {"bf16": ops.sigmoid_ids, "mixed": ops.sigmoid_ids_e4m3,
                     "fp8": ops.sigmoid_ids_fp8}[quant]
             # (partials, g) or, mixed and fp8, (partials, g8, gt8)
             partials, *slabs = emit(zi_k, zt_k, tp_k, bias, img_ids, txt_ids,
                                     duplicates, diag_offset)
+        if save_g:
             sums = partials.double().sum(dim=0)
             ctx.save_for_backward(zimg, ztxt, t_prime, bias, img_ids,
                                   txt_ids, *qts, sums, *slabs)
@@ -165,10 +196,17 @@ class _FusedIdLoss(torch.autograd.Function):
                        else ops.banded_col_step(b))
             loss_only = ops.sigmoid_ids_fp8 if fp8 else ops.sigmoid_ids
             loss = torch.zeros((), device=zimg.device, dtype=torch.float64)
+            if mx:
+                qts = (zi_q, zi_e8, zt_q, zt_e8)   # the bands' recompute
             for j0, j1, diag_j in ops.col_bands(n, step, diag_offset):
-                partials = loss_only(
-                    zi_k, zt_k[j0:j1], tp_k, bias, img_ids,
-                    txt_ids[j0:j1], duplicates, diag_j, want_g=False)[0]
+                labels = (bias, img_ids, txt_ids[j0:j1], duplicates, diag_j)
+                if mx:
+                    partials = ops.sigmoid_ids_mx(
+                        zi_q, zi_e8, zt_q[j0:j1], zt_e8[j0:j1], t_prime,
+                        *labels, want_g=False)[0]
+                else:
+                    partials = loss_only(zi_k, zt_k[j0:j1], tp_k, *labels,
+                                         want_g=False)[0]
                 # the same reduction as saved-g: one block gives the same bits
                 loss = loss + partials.double().sum(dim=0)[0]
             ctx.save_for_backward(zimg, ztxt, t_prime, bias, img_ids,
@@ -184,10 +222,11 @@ class _FusedIdLoss(torch.autograd.Function):
         rest = ctx.saved_tensors[6 + ctx.n_q:]
         n, dev = ztxt.shape[0], zimg.device
         fp8, fp8_gemms = ctx.quant == "fp8", ctx.quant != "bf16"
+        mx = ctx.quant == "mxfp8"
         go = ops._go_scalar(grad_output, dev)
         t = ops._prep_scalar(t_prime, dev).exp()
-        # mixed: one per-tensor quantisation of the embeddings for both GEMMs;
-        # fp8: the forward's.
+        # mixed, mxfp8: one per-tensor quantisation of the embeddings for both
+        # GEMMs; fp8: the forward's.
         qc = None
         if fp8:
             qc = ops.QuantCache.from_tensors(ctx.saved_tensors[6:6 + ctx.n_q])
@@ -218,6 +257,11 @@ class _FusedIdLoss(torch.autograd.Function):
                 if fp8:
                     partials = ops.sigmoid_ids_fp8(
                         qc.zi_q, qc.zt_q[j0:j1], tp_k, *labels, g=g, gt=gt)[0]
+                elif mx:
+                    zi_q, zi_e8, zt_q, zt_e8 = ctx.saved_tensors[6:10]
+                    partials = ops.sigmoid_ids_mx(
+                        zi_q, zi_e8, zt_q[j0:j1], zt_e8[j0:j1], tp_k, *labels,
+                        g=g, gt=gt)[0]
                 elif fp8_gemms:
                     partials = ops.sigmoid_ids_e4m3(
                         zimg, ztxt[j0:j1], tp_k, *labels, g=g, gt=gt)[0]
@@ -289,7 +333,10 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
             docstring); it has no effect on the ``torch`` path, which has no
             fp8 GEMM.  ``"fp8"`` — e4m3 logit operands as well, ``hip`` path
             only (``d % 16 == 0``); with the ``torch`` path, which has no
-            e4m3 logits, it raises ``ValueError``.
+            e4m3 logits, it raises ``ValueError``.  ``"mxfp8"`` — the same
+            with OCP MX block scales, one e8m0 scale per 32 elements, applied
+            in the kernel (``d % 32 == 0``); ``hip`` path only, ``ValueError``
+            with the ``torch`` path.
 
     Returns a 0-d tensor; the caller normalises.
     """
@@ -305,11 +352,11 @@ def sigmoid_contrastive_loss_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
                 and ztxt.dtype == torch.bfloat16 else "torch")
     if impl not in ("hip", "torch"):
         raise ValueError(f"unknown impl {impl!r}")
-    if quant == "fp8" and impl == "torch":
+    if quant in ("fp8", "mxfp8") and impl == "torch":
         # no e4m3 logits here, and bf16-policy values would be a silent lie
         raise ValueError(
-            "quant='fp8' needs the hip path (bf16 embeddings on a GPU); the "
-            "torch path has no e4m3 logits")
+            f"quant={quant!r} needs the hip path (bf16 embeddings on a GPU); "
+            "the torch path has no e4m3 logits")
     img_ids = _ids_vector("img_ids", img_ids, zimg.shape[0], zimg.device)
     txt_ids = _ids_vector("txt_ids", txt_ids, ztxt.shape[0], zimg.device)
     if duplicates != "ignore":

@@ -45,7 +45,10 @@ exposes:
   slab pair (``g`` and ``gᵀ``, ``448·g``) that :func:`grad_gemms` runs on
   hipBLASLt fp8: the ``mixed`` policy of that loss; :func:`sigmoid_ids_fp8`
   — the pass from e4m3 operands on the MX-scaled MFMA (the pair tile's e4m3
-  main loop), loss only or writing the same slab pair: the ``fp8`` policy.
+  main loop), loss only or writing the same slab pair: the ``fp8`` policy;
+  :func:`quantize_mx` and :func:`sigmoid_ids_mx` — OCP MXFP8 operands, one
+  e8m0 scale per 32 elements quantised in one pass and applied by the MFMA
+  (the pair tile's MX main loop): the ``mxfp8`` policy.
 - sample-ID labels for the softmax loss: :func:`pair_lse_ids` — masked row
   and column log-sum-exp plus each row's and column's positive-logit sum and
   positive count — and :func:`softmax_g_ids` — the dL/dlogit slab with
@@ -214,6 +217,11 @@ _EXPORTS = {
     # (stream, zimg_q, ztxt_q, t', bias, img_ids, txt_ids, g8, gt8, ws, b, n,
     #  d, ldg, ldgt, diag, mode)
     "sigmoid_ids_fp8": [_P] * 10 + [_I] * 3 + [_L] * 2 + [_I] * 2,
+    # (stream, x, q, e8, rows, d)
+    "quant_mx_bf16": [_P] * 4 + [_I] * 2,
+    # (stream, zimg_q, zimg_e8, ztxt_q, ztxt_e8, t', bias, img_ids, txt_ids,
+    #  g8, gt8, ws, b, n, d, lde_img, lde_txt, ldg, ldgt, diag, mode)
+    "sigmoid_ids_mx": [_P] * 12 + [_I] * 3 + [_L] * 4 + [_I] * 2,
     "softmax_ids_tile_dim": [],
     # (stream, zimg, ztxt, t', img_ids, txt_ids, row_ws, col_ws, row_lse,
     #  row_pos, row_cnt, col_lse, col_pos, col_cnt, b, n, d, diag, mode)
@@ -443,6 +451,49 @@ def quantize_fp8_pair(zimg: torch.Tensor, ztxt: torch.Tensor) -> QuantCache:
     zi_q, si = _quant_fp8(zimg)
     zt_q, st = _quant_fp8(ztxt)
     return QuantCache(zi_q, zt_q, si, st)
+
+
+def quantize_mx(x: torch.Tensor):
+    """OCP MXFP8 quantisation of ``x`` ``(rows, d)``, ``d % 32 == 0`` →
+    ``(q, e8)``: e4m3 elements with one power-of-two scale per block of 32
+    consecutive elements of a row, what :func:`sigmoid_ids_mx` reads.
+
+    ``q`` is ``(rows, d)`` ``torch.float8_e4m3fn`` and ``e8`` ``(rows,
+    4·ceil(d / 128))`` ``uint8``: byte ``kb`` of a row is the e8m0 code of
+    elements ``32·kb … 32·kb + 31`` (``x ≈ q·2^(code − 127)``), bytes past
+    ``d / 32`` are ``0x7F``, so a row is one aligned dword per 128 elements.
+    Per block, with ``amax = m·2^p``, ``m`` in ``[1, 2)``: ``e = p − 8`` if
+    ``m ≤ 1.75`` else ``p − 7`` — the smallest power of two with ``amax·2^−e ≤
+    448``, nothing saturates — clamped to ``[−127, 127]``; the code is ``e +
+    127``, ``0x7F`` for an all-zero block; the elements are ``x·2^−e`` rounded
+    to nearest even.  Non-finite input is unspecified.
+
+    Contiguous bf16 on a GPU runs the one-pass HIP kernel (no host sync);
+    anything else this torch composite of the same rule, byte for byte."""
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 32 or x.shape[1] % 32:
+        raise RuntimeError(
+            f"quantize_mx needs (rows, d) with rows >= 1 and d a positive "
+            f"multiple of 32 (got {tuple(x.shape)})")
+    rows, d = x.shape
+    width = 4 * (-(-d // 128))
+    if x.is_cuda and x.dtype == torch.bfloat16:
+        lib = _require_lib()
+        xd = x.detach().contiguous()
+        q = torch.empty((rows, d), device=xd.device, dtype=torch.float8_e4m3fn)
+        e8 = torch.empty((rows, width), device=xd.device, dtype=torch.uint8)
+        stream = torch.cuda.current_stream(xd.device).cuda_stream
+        _check(lib.quant_mx_bf16(ctypes.c_void_p(stream), _ptr(xd), _ptr(q),
+                                 _ptr(e8), rows, d), "quant_mx_bf16")
+        return q, e8
+    xf = x.detach().float().reshape(rows, d // 32, 32)
+    mant, exp = torch.frexp(xf.abs().amax(dim=2))     # amax = mant·2^exp
+    e = (exp - 9 + (mant > 0.875).to(exp.dtype)).clamp(-127, 127)   # p = exp−1
+    e = torch.where(mant == 0, torch.zeros_like(e), e)
+    inv = ((127 - e) << 23).to(torch.int32).view(torch.float32)     # 2^−e
+    q = (xf * inv[:, :, None]).to(torch.float8_e4m3fn).reshape(rows, d)
+    e8 = torch.full((rows, width), 0x7F, device=x.device, dtype=torch.uint8)
+    e8[:, :d // 32] = (e + 127).to(torch.uint8)
+    return q, e8
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -1428,6 +1479,88 @@ def sigmoid_ids_fp8(zimg_q: torch.Tensor, ztxt_q: torch.Tensor,
         ctypes.c_longlong(ldgt), _diag_arg(diag_offset),
         _DUPLICATES[duplicates]),
         "sigmoid_ids_fp8")
+    return partials, g, gt
+
+
+def sigmoid_ids_mx(zimg_q: torch.Tensor, zimg_e8: torch.Tensor,
+                   ztxt_q: torch.Tensor, ztxt_e8: torch.Tensor,
+                   t_prime: torch.Tensor, bias: torch.Tensor,
+                   img_ids: torch.Tensor, txt_ids: torch.Tensor,
+                   duplicates: str = "positive",
+                   diag_offset: Optional[int] = None,
+                   g: Optional[torch.Tensor] = None,
+                   gt: Optional[torch.Tensor] = None, want_g: bool = True):
+    """:func:`sigmoid_ids` from MXFP8 operands — e4m3 elements with one e8m0
+    scale per 32 consecutive ``k``, applied by the MX-scaled MFMA itself: the
+    ``mxfp8`` policy of that loss → ``(partials, g | None, gt | None)``.
+
+    ``zimg_q`` ``(b, d)`` / ``ztxt_q`` ``(n, d)`` and ``zimg_e8`` ``(b, w)`` /
+    ``ztxt_e8`` ``(n, w)``, ``w = 4·ceil(d / 128)``, are :func:`quantize_mx`'s
+    pairs: contiguous ``float8_e4m3fn`` and ``uint8`` on one GPU, ``d % 32 ==
+    0``, the scales 4-byte aligned (a row slice of either pair qualifies).
+    ``s`` is the true dot of the dequantised values ``q·2^(code − 127)`` and
+    ``z = exp(t_prime)·s + bias``: ``t_prime`` is passed unchanged.
+
+    Slabs, ``want_g``, labels, scalars and ``partials`` as
+    :func:`sigmoid_ids_fp8`; with every scale byte ``0x7F`` the results are
+    that function's bit for bit.  Every failure raises before any launch.  No
+    autograd."""
+    E4M3 = torch.float8_e4m3fn
+    for what, x, dt in (("zimg_q", zimg_q, E4M3), ("ztxt_q", ztxt_q, E4M3),
+                        ("zimg_e8", zimg_e8, torch.uint8),
+                        ("ztxt_e8", ztxt_e8, torch.uint8)):
+        if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != dt
+                or not x.is_cuda or not x.is_contiguous()):
+            raise RuntimeError(
+                f"sigmoid_ids_mx: {what} must be a contiguous {dt} 2-D GPU "
+                f"tensor (got {getattr(x, 'dtype', type(x))} "
+                f"{tuple(getattr(x, 'shape', ()))} on "
+                f"{getattr(x, 'device', None)})")
+    (b, d), n, dev = zimg_q.shape, ztxt_q.shape[0], zimg_q.device
+    if ztxt_q.shape[1] != d or any(
+            x.device != dev for x in (zimg_e8, ztxt_q, ztxt_e8)):
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings on one device, got "
+            f"{tuple(zimg_q.shape)} and {tuple(ztxt_q.shape)}")
+    if b < 1 or n < 1:
+        raise RuntimeError("sigmoid_ids_mx needs a non-empty block")
+    if d % 32 != 0:
+        raise RuntimeError(
+            f"emb dim must be a multiple of 32 for mxfp8 (got {d})")
+    width = 4 * (-(-d // 128))
+    for what, e8, rows in (("zimg_e8", zimg_e8, b), ("ztxt_e8", ztxt_e8, n)):
+        if tuple(e8.shape) != (rows, width):
+            raise RuntimeError(
+                f"sigmoid_ids_mx: {what} must have shape ({rows}, {width}) "
+                f"(got {tuple(e8.shape)})")
+        if e8.data_ptr() % 4 != 0:
+            raise RuntimeError(
+                f"sigmoid_ids_mx: {what} must be 4-byte aligned")
+    _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
+    ldg, ldgt = n, b
+    if not want_g:
+        if g is not None or gt is not None:
+            raise RuntimeError("g / gt given with want_g=False")
+    elif (g is None) != (gt is None):
+        raise RuntimeError("g and gt must be given together (or neither)")
+    else:
+        g, ldg = _g_view(g, b, n, dev, E4M3)
+        gt, ldgt = _g_view(gt, n, b, dev, E4M3, "gt")
+    lib = _require_lib()
+    tile = lib.sigmoid_ids_tile_dim()
+    tp, bp = _prep_scalar(t_prime, dev), _prep_scalar(bias, dev)
+    partials = torch.empty((-(-b // tile) * -(-n // tile), 3), device=dev,
+                           dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.sigmoid_ids_mx(
+        ctypes.c_void_p(stream), _ptr(zimg_q), _ptr(zimg_e8), _ptr(ztxt_q),
+        _ptr(ztxt_e8), _ptr(tp), _ptr(bp), _ptr(img_ids), _ptr(txt_ids),
+        _ptr(g), _ptr(gt), _ptr(partials), b, n, d,
+        ctypes.c_longlong(width), ctypes.c_longlong(width),
+        ctypes.c_longlong(ldg),
+        ctypes.c_longlong(ldgt), _diag_arg(diag_offset),
+        _DUPLICATES[duplicates]),
+        "sigmoid_ids_mx")
     return partials, g, gt
 
 

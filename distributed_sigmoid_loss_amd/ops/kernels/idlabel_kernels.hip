@@ -46,6 +46,16 @@
 // the raw dot of the e4m3 values and the per-tensor scales arrive folded into
 // t'; row-wise scales are not built.
 //
+// MX operands (the `mxfp8` policy).  A third operand type, mx_e4m3: the same
+// e4m3 bytes with one e8m0 scale per 32 consecutive k (OCP MXFP8), read by
+// pair_tile.h's MX main loop, which stages the scale dwords next to the
+// element slabs and hands each MFMA its lanes' block scales.  s is then the
+// true dot of the dequantised values and t' arrives unchanged.  Two more
+// kernels, sigmoid_ids_mx_kernel<false> (G_NONE) and <true> (G_E4M3), with
+// 66 KiB of LDS (still two workgroups per CU) and without packed fp32
+// instructions: with every scale byte 0x7F they leave the bits of the fp8
+// pair.  Everything after the K loop is the same code.
+//
 // Structure.  The tile, its main loop (text fragment first: lane l owns image
 // row (l & 15) and the four consecutive text columns 4·(l >> 4) … +3 of each
 // fragment), the block walk, the id staging and the g
@@ -65,9 +75,15 @@
 
 #include "pair_tile.h"
 
+#include <type_traits>
+
 namespace {
 
 enum { G_NONE = 0, G_BF16 = 1, G_E4M3 = 2 };
+
+// Operand element of the MX kernels: an e4m3 byte whose scale lives in a
+// separate e8m0 array (the tile body's zimg_e8 / ztxt_e8 / lde).
+enum mx_e4m3 : unsigned char {};
 
 // 128 row ids and 128 column ids above the g staging, then 4 waves × 3
 // partials.
@@ -85,7 +101,9 @@ static_assert(red_off(G_BF16) + 64 <= 2 * BUF_BYTES &&
 // One tile: g is the bf16 slab (G_BF16) or the e4m3 slab (G_E4M3), gt the
 // e4m3 transpose (G_E4M3 only).  OP is the operand element: __bf16, or
 // unsigned char for e4m3 (s is then the raw dot of the e4m3 values and
-// tprime holds the folded scales).  `lds` is the workgroup's 2 · BUF_BYTES.
+// tprime holds the folded scales), or mx_e4m3 with the block scales in
+// zimg_e8 / ztxt_e8, rows lde bytes apart (s is the true dot).  `lds` is the
+// workgroup's 2 · BUF_BYTES, MX_LDS_BYTES for mx_e4m3.
 template <int GFMT, typename OP = __bf16>
 __device__ __forceinline__ void sigmoid_ids_tile(
     const OP* __restrict__ zimg, const OP* __restrict__ ztxt,
@@ -94,12 +112,18 @@ __device__ __forceinline__ void sigmoid_ids_tile(
     const long long* __restrict__ txt_ids, void* __restrict__ g,
     void* __restrict__ gt, float* __restrict__ ws, int b, int n, int d,
     long long ldg, long long ldgt, int diag, int ignore_dups, int tiles_m,
-    int tiles_n, unsigned char* lds) {
+    int tiles_n, unsigned char* lds,
+    const unsigned char* __restrict__ zimg_e8 = nullptr,
+    const unsigned char* __restrict__ ztxt_e8 = nullptr, int lde = 0) {
   constexpr int IDS_OFF = ids_off(GFMT), RED_OFF = red_off(GFMT);
   const TilePos tp = tile_of_block(tiles_m, tiles_n);
   const int m0 = tp.tm * BM, n0 = tp.tn * BN;
   f32x4 acc[4][4];
-  if constexpr (sizeof(OP) == 1)
+  if constexpr (std::is_same<OP, mx_e4m3>::value)
+    pair_tile_dots_mx<true>((const unsigned char*)zimg, zimg_e8,
+                            (const unsigned char*)ztxt, ztxt_e8, b, n, d, lde,
+                            m0, n0, lds, acc);
+  else if constexpr (sizeof(OP) == 1)
     pair_tile_dots_e4m3<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
   else
     pair_tile_dots<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
@@ -255,6 +279,28 @@ __launch_bounds__(NTHREADS) __global__ void sigmoid_ids_fp8_kernel(
       ldg, ldgt, diag, ignore_dups, tiles_m, tiles_n, lds);
 }
 
+// MX operands (the `mxfp8` policy): the fp8 pair's two forms with the e8m0
+// block scales of both operands, one dword per row and 128-element K-step.
+template <bool WRITE_G>
+__attribute__((target("no-packed-fp32-ops")))
+__launch_bounds__(NTHREADS) __global__ void sigmoid_ids_mx_kernel(
+    const unsigned char* __restrict__ zimg_q,
+    const unsigned char* __restrict__ zimg_e8,
+    const unsigned char* __restrict__ ztxt_q,
+    const unsigned char* __restrict__ ztxt_e8,
+    const float* __restrict__ tprime, const float* __restrict__ bias,
+    const long long* __restrict__ img_ids,
+    const long long* __restrict__ txt_ids, unsigned char* __restrict__ g8,
+    unsigned char* __restrict__ gt8, float* __restrict__ ws, int b, int n,
+    int d, int lde, long long ldg, long long ldgt, int diag, int ignore_dups,
+    int tiles_m, int tiles_n) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[MX_LDS_BYTES];
+  sigmoid_ids_tile<WRITE_G ? G_E4M3 : G_NONE, mx_e4m3>(
+      (const mx_e4m3*)zimg_q, (const mx_e4m3*)ztxt_q, tprime, bias, img_ids,
+      txt_ids, g8, gt8, ws, b, n, d, ldg, ldgt, diag, ignore_dups, tiles_m,
+      tiles_n, lds, zimg_e8, ztxt_e8, lde);
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,6 +415,47 @@ int sigmoid_ids_fp8(uintptr_t stream, const void* zimg_q, const void* ztxt_q,
                      (const long long*)txt_ids, (unsigned char*)g8,
                      (unsigned char*)gt8, (float*)ws, b, n, d, ldg, ldgt, diag,
                      mode, tiles_m, tiles_n);
+  return (int)hipGetLastError();
+}
+
+// The loss from MX operands: zimg_q (b, d), ztxt_q (n, d) OCP e4m3fn bytes,
+// row-major contiguous, d a multiple of 32; zimg_e8 (b rows), ztxt_e8 (n
+// rows) their e8m0 block scales, byte kb of a row for elements 32·kb … +31,
+// 4-byte aligned with rows lde_img / lde_txt bytes apart, both exactly
+// 4·ceil(d / 128) (bytes past d / 32 are not applied to anything: their
+// elements are zero-filled).  s is the true dot Σ 2^(ea + eb − 254)·a·b and
+// z = exp(*tprime)·s + bias.  Slabs, ws, labels and every other check as
+// sigmoid_ids_fp8; with every scale byte 0x7F its bits.  Returns non-zero,
+// launching nothing, on anything unsupported.
+int sigmoid_ids_mx(uintptr_t stream, const void* zimg_q, const void* zimg_e8,
+                   const void* ztxt_q, const void* ztxt_e8,
+                   const void* tprime, const void* bias, const void* img_ids,
+                   const void* txt_ids, void* g8, void* gt8, void* ws, int b,
+                   int n, int d, long long lde_img, long long lde_txt,
+                   long long ldg, long long ldgt, int diag, int mode) {
+  if (!pair_dims_ok_mx(zimg_q, zimg_e8, ztxt_q, ztxt_e8, b, n, d, lde_img,
+                       lde_txt) ||
+      tprime == nullptr || bias == nullptr || img_ids == nullptr ||
+      txt_ids == nullptr || ws == nullptr ||
+      (g8 == nullptr) != (gt8 == nullptr) || (mode != 0 && mode != 1))
+    return (int)hipErrorInvalidValue;
+  if (((uintptr_t)img_ids | (uintptr_t)txt_ids) % 8 != 0 ||
+      ((uintptr_t)tprime | (uintptr_t)bias | (uintptr_t)ws) % 4 != 0)
+    return (int)hipErrorInvalidValue;
+  if (g8 != nullptr && (ldg < n || ldgt < b)) return (int)hipErrorInvalidValue;
+  const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
+  if (!pair_grid_ok(tiles_m, tiles_n)) return (int)hipErrorInvalidValue;
+  const auto kernel = g8 != nullptr ? sigmoid_ids_mx_kernel<true>
+                                    : sigmoid_ids_mx_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(tiles_m * tiles_n), dim3(NTHREADS), 0,
+                     (hipStream_t)stream, (const unsigned char*)zimg_q,
+                     (const unsigned char*)zimg_e8,
+                     (const unsigned char*)ztxt_q,
+                     (const unsigned char*)ztxt_e8, (const float*)tprime,
+                     (const float*)bias, (const long long*)img_ids,
+                     (const long long*)txt_ids, (unsigned char*)g8,
+                     (unsigned char*)gt8, (float*)ws, b, n, d, (int)lde_img,
+                     ldg, ldgt, diag, mode, tiles_m, tiles_n);
   return (int)hipGetLastError();
 }
 

@@ -365,6 +365,189 @@ __device__ __forceinline__ void pair_tile_dots_e4m3(
   }
 }
 
+// The main loop for MX operands (OCP MXFP8: e4m3 elements, one e8m0 scale per
+// 32 consecutive k): zimg_q / ztxt_q as for pair_tile_dots_e4m3 with
+// d % 32 == 0; zimg_e8 (b rows) and ztxt_e8 (n rows) hold one dword per row
+// and 128-element K-step, byte kb of a row the e8m0 code of K-block kb, rows
+// `lde` bytes apart (lde % 4 == 0, 4-byte aligned, at least 4·ceil(d / 128)).
+// The contract of pair_tile_dots_e4m3 — acc layouts, zero-fill, 64-bit
+// offsets, the closing barrier — except that acc holds the true dots
+//   Σ_kb 2^(ea_kb − 127)·2^(eb_kb − 127)·Σ_{k in kb} a_k·b_k,
+// the scaling done by the MFMA, and that `lds` holds MX_LDS_BYTES: the
+// element slabs, staging thread map, lds_off and swizzle are the e4m3 loop's,
+// and the 2 × 1 KiB above them take the scales.
+//
+// Fragments.  The instruction's k order is not the e4m3 loop's: lane l holds
+// k = 16·(l >> 4) … +15 in its first four registers and k = 64 + 16·(l >> 4)
+// … +15 in the other four, and scales the 32-element block of hardware k
+// 32·kb … +31 by what lane group kb supplies (measured:
+// tools/probe_mx_scale_map.hip sweeps every lane and byte of both scale
+// operands; tools/probe_mx_rowscale.hip, with one scale per row, cannot
+// tell).  With unit scales any pairing of equal k on both sides will do, which
+// is what the e4m3 loop relies on; here a block must be 32 consecutive k of
+// the row, so a lane reads chunks fq and 4 + fq of its fragment row instead
+// of 2·fq and 2·fq + 1 — the bf16 loop's read pattern, conflict-free for the
+// same reason.
+//
+// Scales.  Per step thread t < 128 loads image row m0 + t's dword, thread
+// 128 + t text row n0 + t's (0x7F7F7F7F, 2⁰, for a row outside the block or a
+// step past the scale row), together with its element chunks, and stores it
+// with them: [128 image dwords][128 text dwords] per buffer, published by the
+// barrier that publishes the elements.  The MFMA takes from lane l the scale
+// of row l & 15, K-block l >> 4 — the lane's own fragment row and the byte
+// fq = l >> 4 of that row's dword — so a lane reads the dword of each of its
+// 4 + 4 fragment rows (16 consecutive dwords over a fragment's rows and the
+// same address over its four K-blocks: conflict-free broadcasts) and one
+// v_perm_b32 copies byte fq into all four bytes (the instruction reads the
+// byte its op_sel names, byte 0 here).  8 ds_read_b32 and 8 v_perm_b32 per step against 40
+// ds_read_b128 and 16 MFMAs; 8 more VGPRs than the e4m3 loop, the four text
+// scales resident with their fragments, the image scales of the step too.
+constexpr int MX_SCALE_BYTES = (BM + BN) * 4;              // one buffer: 1 KiB
+constexpr int MX_LDS_BYTES = 2 * BUF_BYTES + 2 * MX_SCALE_BYTES;   // 66 KiB
+
+// d a positive multiple of 32 on top of pair_dims_ok_e4m3, and scale rows of
+// exactly one aligned dword per K-step.
+inline bool pair_dims_ok_mx(const void* zimg_q, const void* zimg_e8,
+                            const void* ztxt_q, const void* ztxt_e8, int b,
+                            int n, int d, long long lde_img,
+                            long long lde_txt) {
+  if (!pair_dims_ok_e4m3(zimg_q, ztxt_q, b, n, d) || d % 32 != 0) return false;
+  if (zimg_e8 == nullptr || ztxt_e8 == nullptr) return false;
+  if (((uintptr_t)zimg_e8 | (uintptr_t)ztxt_e8) % 4 != 0) return false;
+  const long long want = 4ll * ceil_div(d, BK8);
+  return lde_img == want && lde_txt == want;
+}
+
+template <bool TEXT_FIRST>
+__device__ __forceinline__ void pair_tile_dots_mx(
+    const unsigned char* __restrict__ zimg_q,
+    const unsigned char* __restrict__ zimg_e8,
+    const unsigned char* __restrict__ ztxt_q,
+    const unsigned char* __restrict__ ztxt_e8, int b, int n, int d, int lde,
+    int m0, int n0, unsigned char* lds, f32x4 (&acc)[4][4]) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+
+  // Staging: thread t owns chunk t&7 of rows (t>>3) + 32·i, i = 0..3.
+  const int ld_ch = tid & 7;
+  const int ld_row = tid >> 3;
+  const unsigned char* a_src[LOADS];
+  const unsigned char* b_src[LOADS];
+  bool a_ok[LOADS], b_ok[LOADS];
+  int st_off[LOADS];
+#pragma unroll
+  for (int i = 0; i < LOADS; ++i) {
+    const int row = ld_row + 32 * i;
+    a_ok[i] = m0 + row < b;
+    b_ok[i] = n0 + row < n;
+    a_src[i] = zimg_q + (long long)(m0 + row) * d + ld_ch * 16;
+    b_src[i] = ztxt_q + (long long)(n0 + row) * d + ld_ch * 16;
+    st_off[i] = lds_off(row, ld_ch);
+  }
+  // ... and the scale dword of one row: image rows first.
+  const bool sc_img = tid < BM;
+  const int sc_row = sc_img ? m0 + tid : n0 + (tid - BM);
+  const bool sc_ok = sc_row < (sc_img ? b : n);
+  const unsigned char* sc_src =
+      (sc_img ? zimg_e8 : ztxt_e8) + (long long)sc_row * lde;
+  unsigned char* sc_lds = lds + 2 * BUF_BYTES;
+
+  // Fragment reads: lane l takes row (l & 15), k = 16·(l >> 4) … +15 and
+  // 64 + 16·(l >> 4) … +15 of the 128-deep MFMA step: chunks fq and 4 + fq.
+  const int fr = lane & 15, fq = lane >> 4;
+  int a_off[4][2], b_off[4][2];
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      a_off[f][h] = lds_off(wm * 64 + f * 16 + fr, 4 * h + fq);
+      b_off[f][h] = OP_BYTES + lds_off(wn * 64 + f * 16 + fr, 4 * h + fq);
+    }
+  const int sa_off = 4 * (wm * 64 + fr), sb_off = 4 * (BM + wn * 64 + fr);
+  const unsigned fq_sel = 0x01010101u * (unsigned)fq;   // v_perm: byte fq × 4
+
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  uint4 ra[LOADS], rb[LOADS];
+  unsigned rs;
+
+  auto load_step = [&](int s) {
+    const int k0 = s * BK8;
+    const bool k_ok = k0 + ld_ch * 16 < d;    // d % 16 == 0: all or nothing
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      ra[i] = uint4{0u, 0u, 0u, 0u};
+      rb[i] = uint4{0u, 0u, 0u, 0u};
+      if (k_ok && a_ok[i])
+        ra[i] = *reinterpret_cast<const uint4*>(a_src[i] + k0);
+      if (k_ok && b_ok[i])
+        rb[i] = *reinterpret_cast<const uint4*>(b_src[i] + k0);
+    }
+    rs = (unsigned)MX_UNIT_SCALE;
+    if (sc_ok && 4 * s + 4 <= lde)
+      rs = *reinterpret_cast<const unsigned*>(sc_src + 4 * s);
+  };
+  auto store_step = [&](int buf) {
+    unsigned char* base = lds + buf * BUF_BYTES;
+#pragma unroll
+    for (int i = 0; i < LOADS; ++i) {
+      *reinterpret_cast<uint4*>(base + st_off[i]) = ra[i];
+      *reinterpret_cast<uint4*>(base + OP_BYTES + st_off[i]) = rb[i];
+    }
+    *reinterpret_cast<unsigned*>(sc_lds + buf * MX_SCALE_BYTES + 4 * tid) = rs;
+  };
+  auto fragment = [](const unsigned char* base, const int (&off)[2]) {
+    const uint4 lo = *reinterpret_cast<const uint4*>(base + off[0]);
+    const uint4 hi = *reinterpret_cast<const uint4*>(base + off[1]);
+    return i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w,
+                 (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+  };
+  // Byte fq of fragment f's scale dword, in every byte.
+  auto scale = [&](const unsigned char* sc, int off, int f) {
+    const unsigned w = *reinterpret_cast<const unsigned*>(sc + off + 64 * f);
+    return (int)__builtin_amdgcn_perm(0u, w, fq_sel);
+  };
+
+  const int nsteps = (d + BK8 - 1) / BK8;
+  load_step(0);
+  store_step(0);
+  __syncthreads();
+
+  for (int s = 0; s < nsteps; ++s) {
+    const bool more = s + 1 < nsteps;
+    if (more) load_step(s + 1);
+
+    const unsigned char* base = lds + (s & 1) * BUF_BYTES;
+    const unsigned char* sc = sc_lds + (s & 1) * MX_SCALE_BYTES;
+    i32x8 bfr[4];
+    int sa[4], sb[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+      bfr[f] = fragment(base, b_off[f]);
+      sa[f] = scale(sc, sa_off, f);
+      sb[f] = scale(sc, sb_off, f);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const i32x8 af = fragment(base, a_off[i]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            TEXT_FIRST ? bfr[j] : af, TEXT_FIRST ? af : bfr[j], acc[i][j],
+            0, 0,                                   // both operands e4m3
+            0, TEXT_FIRST ? sb[j] : sa[i], 0, TEXT_FIRST ? sa[i] : sb[j]);
+    }
+
+    if (more) store_step((s + 1) & 1);
+    __syncthreads();
+  }
+}
+
 // Column of row `row`'s positive, j == row + diag; −1 when there is none in
 // the block (diag == DIAG_NONE, or the column falls outside [0, n)).
 __device__ __forceinline__ int positive_col(int row, int diag, int n) {

@@ -3,7 +3,7 @@ kernel at the same shape and against the stock composite it replaces, in one
 process.
 
     python tools/idlabel_probe.py [--batch 32768 8192] [--dim 768] [--iters 30]
-                                  [--quant bf16|mixed|fp8]
+                                  [--quant bf16|mixed|fp8|mxfp8]
                                   [--only all|loss|g|g8|loss8|pair8]
 
 At each (B, B, d) bf16 shape, L2-normalised inputs, ``t = 10``, ``bias =
@@ -38,6 +38,18 @@ timed calls and its scales are added to ``t'``:
 - ``pair8`` against ``g8``: ``ops.sigmoid_ids_fp8`` writing the slab pair
   against ``ops.sigmoid_ids_e4m3``, into the same buffers;
 - ``fp8`` against ``mixed``: fused forward + backward, and the peak memory.
+
+``--quant mxfp8`` is the row set of the ``mxfp8`` policy, next to the ``fp8``
+one in alternating pairs, GEMM table loaded, both quantisations made once
+outside the timed kernel calls:
+
+- ``quant_mx`` against ``quant_fp8``: ``ops.quantize_mx`` on both operands
+  against ``ops.quantize_fp8_pair``;
+- ``loss_mx`` against ``loss8``: ``ops.sigmoid_ids_mx(want_g=False)`` against
+  ``ops.sigmoid_ids_fp8(want_g=False)``;
+- ``pair_mx`` against ``pair8``: both writing the slab pair, into the same
+  buffers;
+- ``mxfp8`` against ``fp8``: fused forward + backward, and the peak memory.
 
 ``fused`` and ``stock`` are timed alternately, call by call, so that drift of
 the clocks hits both alike.  Peak memory of each is the growth of
@@ -128,6 +140,8 @@ def probe(b, d, iters, only, quant="bf16"):
         out.update({f"{name}_ms": stats[0], f"{name}_min_ms": stats[1],
                     f"{name}_max_ms": stats[2]})
 
+    if quant == "mxfp8":
+        return probe_mx(out, zi, zt, tp, bias, img_ids, txt_ids, iters)
     if quant == "fp8" or only in ("loss8", "pair8"):
         return probe_fp8(out, zi, zt, tp, bias, img_ids, txt_ids, iters, only)
     if quant == "mixed" or only == "g8":
@@ -282,6 +296,54 @@ def probe_fp8(out, zi, zt, tp, bias, img_ids, txt_ids, iters, only):
     return out
 
 
+def probe_mx(out, zi, zt, tp, bias, img_ids, txt_ids, iters):
+    b = zi.shape[0]
+    out["quant"] = "mxfp8"
+    out["tuned_gemms"] = ops.load_tuned_gemms()
+    flop = 2.0 * b * b * zi.shape[1]
+
+    def pair(a, b_, stats_a, stats_b):
+        for name, st in ((a, stats_a), (b_, stats_b)):
+            out.update({f"{name}_ms": st[0], f"{name}_min_ms": st[1],
+                        f"{name}_max_ms": st[2]})
+        out[f"{a}_over_{b_}"] = round(out[f"{a}_ms"] / out[f"{b_}_ms"], 3)
+
+    pair("quant_mx", "quant_fp8", *alternate_ms(
+        lambda: (ops.quantize_mx(zi), ops.quantize_mx(zt)),
+        lambda: ops.quantize_fp8_pair(zi, zt), iters))
+    qc = ops.quantize_fp8_pair(zi, zt)
+    tp8 = tp + qc.si.log() + qc.st.log()
+    mx = (*ops.quantize_mx(zi), *ops.quantize_mx(zt))
+    ids = (bias, img_ids, txt_ids)
+    g8 = torch.empty((b, b), device="cuda", dtype=torch.float8_e4m3fn)
+    gt8 = torch.empty((b, b), device="cuda", dtype=torch.float8_e4m3fn)
+    pair("loss_mx", "loss8", *alternate_ms(
+        lambda: ops.sigmoid_ids_mx(*mx, tp, *ids, want_g=False),
+        lambda: ops.sigmoid_ids_fp8(qc.zi_q, qc.zt_q, tp8, *ids, want_g=False),
+        iters))
+    out["loss_mx_tflops"] = round(flop / out["loss_mx_ms"] * 1e-9, 1)
+    pair("pair_mx", "pair8", *alternate_ms(
+        lambda: ops.sigmoid_ids_mx(*mx, tp, *ids, g=g8, gt=gt8),
+        lambda: ops.sigmoid_ids_fp8(qc.zi_q, qc.zt_q, tp8, *ids, g=g8, gt=gt8),
+        iters))
+    del g8, gt8
+
+    leaves = [x.clone().requires_grad_() for x in (zi, zt, tp, bias)]
+
+    def step(quant):
+        def run():
+            for x in leaves:
+                x.grad = None
+            sigmoid_contrastive_loss_ids(*leaves, img_ids, txt_ids,
+                                         impl="hip", quant=quant).backward()
+        return run
+
+    pair("mxfp8", "fp8", *alternate_ms(step("mxfp8"), step("fp8"), iters))
+    out["mxfp8_peak_mib"] = peak_mib(step("mxfp8"))
+    out["fp8_peak_mib"] = peak_mib(step("fp8"))
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, nargs="+", default=[32768, 8192])
@@ -290,7 +352,7 @@ def main():
     p.add_argument("--only",
                    choices=["all", "loss", "g", "g8", "loss8", "pair8"],
                    default="all")
-    p.add_argument("--quant", choices=["bf16", "mixed", "fp8"],
+    p.add_argument("--quant", choices=["bf16", "mixed", "fp8", "mxfp8"],
                    default="bf16")
     args = p.parse_args()
     if not torch.cuda.is_available():

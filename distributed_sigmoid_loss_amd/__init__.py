@@ -49,6 +49,11 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
   other caption of the same image, repeated sample or padding column is
   returned as a "hard negative"; a fused HIP kernel that turns the ids into
   per-lane class bits before each tile's dot products.
+- ``sigmoid_distillation_loss`` / ``DistributedSigmoidDistillLoss`` — the
+  sigmoid loss against soft targets: a teacher dual encoder's own pair
+  probabilities, mixed with the hard label, from a fused HIP kernel that runs
+  the teacher's and the student's dot products on each tile and keeps the
+  targets in registers; neither ``(b, n)`` grid is built.
 
 The compute path is PyTorch-ROCm + HIP/CDNA4 kernels + RCCL over xGMI; there
 are no CUDA compatibility layers and no multi-backend dispatch.
@@ -84,6 +89,10 @@ from .losses.softmax_loss import (
     softmax_contrastive_loss_ids,
 )
 from .losses.id_labels import sigmoid_contrastive_loss_ids
+from .losses.distill import (
+    DistributedSigmoidDistillLoss,
+    sigmoid_distillation_loss,
+)
 from .parallel.ring import (
     neighbour_exchange,
     neighbour_exchange_bidir,
@@ -118,6 +127,8 @@ __all__ = [
     "softmax_contrastive_loss",
     "softmax_contrastive_loss_ids",
     "sigmoid_contrastive_loss_ids",
+    "DistributedSigmoidDistillLoss",
+    "sigmoid_distillation_loss",
     "neighbour_exchange",
     "neighbour_exchange_bidir",
     "neighbour_exchange_with_grad",

@@ -10,9 +10,14 @@ from .retrieval import (
 )
 from .softmax_loss import DistributedSoftmaxLoss, softmax_contrastive_loss
 from .id_labels import sigmoid_contrastive_loss_ids
+from .distill import (
+    DistributedSigmoidDistillLoss,
+    sigmoid_distillation_loss,
+)
 
 __all__ = ["DistributedSigmoidLoss", "SigLipLoss", "sigmoid_contrastive_loss",
            "RetrievalRanks", "pair_rank_counts", "positive_scores",
            "retrieval_ranks", "recall_at_k", "distributed_retrieval_ranks",
            "DistributedSoftmaxLoss", "softmax_contrastive_loss",
-           "sigmoid_contrastive_loss_ids"]
+           "sigmoid_contrastive_loss_ids", "DistributedSigmoidDistillLoss",
+           "sigmoid_distillation_loss"]

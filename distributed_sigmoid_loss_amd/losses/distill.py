@@ -1,0 +1,285 @@
+"""Sigmoid distillation loss: soft targets from a teacher dual encoder.
+
+Every other loss of the package takes hard labels.  The usual recipe for
+training a small image–text model with a sigmoid loss is distillation from a
+larger dual encoder: the teacher's own pair grid is the soft target of every
+student pair, usually mixed with the hard positional label.  The teacher
+embeddings come per sample — ``timg (b, d_T)``, ``ttxt (n, d_T)`` — so the
+target grid is a second ``(b, n)`` matrix of dot products, and like the
+student's it is never built here.
+
+One contract for every implementation.  With ``t = exp(t_prime)`` and
+``t_T = exp(teacher_t_prime)``:
+
+    s_ij = <zimg_i, ztxt_j>          z_ij = t·s_ij + bias
+    p_ij = σ(t_T·<timg_i, ttxt_j> + teacher_bias)
+    q_ij = alpha·p_ij + (1 − alpha)·[j == i + diag_offset]
+    total = Σ_ij softplus(z_ij) − q_ij·z_ij
+    g_ij  = σ(z_ij) − q_ij
+    dzimg = t·g@ztxt   dztxt = t·gᵀ@zimg   dt' = t·Σ g_ij·s_ij   dbias = Σ g_ij
+
+``total`` is the binary cross-entropy of ``σ(z)`` against the target ``q`` in
+sum form; the caller normalises.  It is linear in the target, so the mixed
+objective costs one student pass, not two.  ``alpha = 0`` is
+``sigmoid_contrastive_loss(diag_offset=…)``; ``alpha = 1`` is pure
+distillation, minimal where the student's pair probabilities equal the
+teacher's; ``diag_offset=None`` leaves out the hard positive.  The teacher
+side gets no gradient: its embeddings and scalars are detached.
+
+On GPU (all four embeddings bf16) the fused kernel ``ops.sigmoid_distill``
+runs the teacher's and the student's K loops back to back on each 128×128
+tile and keeps the targets in registers, in the two regimes of the sample-ID
+loss:
+
+- *saved-g* — gradients wanted, ``col_chunk is None`` and the bf16 g slab
+  below 2³² bytes: the forward emits the loss partials and the dL/dlogit slab
+  in one pass; the backward is the two gradient GEMMs (``ops.grad_gemms``)
+  plus the scalar gradients from the saved partials.
+- *band recompute* — otherwise: the forward runs the loss-only kernel per
+  column band (``ztxt`` and ``ttxt`` sliced by the same rows); the backward
+  re-runs the kernel per band through ``ops.band_grad_gemms``.
+
+Per-tile partials are summed in fp64 on the device; nothing syncs with the
+host.  Elsewhere a differentiable torch composite with the same contract runs
+(fp32 compute, fp64 for fp64 inputs) — the CPU path and the tests' reference.
+
+Not built: sample-ID masks with soft targets, quantised operands for either
+pair, the softmax / KL form, the ring strategy.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+import torch.distributed as dist
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import ops
+from ..parallel.collectives import all_gather_with_grad
+
+
+def _torch_distill(zimg, ztxt, t_prime, bias, timg, ttxt, teacher_t_prime,
+                   teacher_bias, alpha, diag_offset, col_chunk):
+    """Differentiable composite, chunked over columns: holds ``O(b ·
+    col_chunk)`` logits and targets at a time."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    cdt = torch.float64 if zimg.dtype == torch.float64 else torch.float32
+    dev = zimg.device
+    zi, ti = zimg.to(cdt), timg.detach().to(cdt)
+    t = t_prime.to(device=dev, dtype=cdt).exp()
+    bs = bias.to(device=dev, dtype=cdt)
+    tt = torch.as_tensor(teacher_t_prime, dtype=cdt,
+                         device=dev).detach().exp()
+    bt = torch.as_tensor(teacher_bias, dtype=cdt, device=dev).detach()
+    rows = torch.arange(b, device=dev)
+    step = int(col_chunk) if col_chunk and col_chunk > 0 else n
+    total = None
+    for j0 in range(0, n, step):
+        j1 = min(j0 + step, n)
+        logits = zi @ ztxt[j0:j1].to(cdt).T * t + bs
+        q = alpha * torch.sigmoid(ti @ ttxt[j0:j1].detach().to(cdt).T * tt
+                                  + bt)
+        if diag_offset is not None:
+            cols = rows + (int(diag_offset) - j0)
+            ok = (cols >= 0) & (cols < j1 - j0)
+            q[rows[ok], cols[ok]] += 1.0 - alpha
+        # softplus(z) − q·z, evaluated without cancellation
+        part = F.binary_cross_entropy_with_logits(logits, q, reduction="sum")
+        total = part if total is None else total + part
+    return total
+
+
+class _FusedDistillLoss(torch.autograd.Function):
+    """GPU path: ``ops.sigmoid_distill`` plus the library gradient GEMMs, in
+    the saved-g or the band-recompute regime (module docstring)."""
+
+    @staticmethod
+    def forward(ctx, zimg, ztxt, t_prime, bias, timg, ttxt, teacher_t_prime,
+                teacher_bias, alpha, diag_offset, col_chunk, want_grad):
+        zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
+        timg, ttxt = timg.contiguous(), ttxt.contiguous()
+        b, n = zimg.shape[0], ztxt.shape[0]
+        teacher = (timg, ttxt, teacher_t_prime, teacher_bias)
+        # want_grad comes from the caller (grad mode is off in here).
+        save_g = want_grad and col_chunk is None and b * n * 2 < 2 ** 32
+        if save_g:
+            partials, g = ops.sigmoid_distill(
+                zimg, ztxt, t_prime, bias, *teacher, alpha, diag_offset)
+            sums = partials.double().sum(dim=0)
+            ctx.save_for_backward(zimg, ztxt, t_prime, bias, sums, g)
+            loss = sums[0]
+        else:
+            step = min(n, int(col_chunk) if col_chunk and col_chunk > 0
+                       else ops.banded_col_step(b))
+            loss = torch.zeros((), device=zimg.device, dtype=torch.float64)
+            for j0, j1, diag_j in ops.col_bands(n, step, diag_offset):
+                partials = ops.sigmoid_distill(
+                    zimg, ztxt[j0:j1], t_prime, bias, timg, ttxt[j0:j1],
+                    teacher_t_prime, teacher_bias, alpha, diag_j,
+                    want_g=False)[0]
+                # the same reduction as saved-g: one block gives the same bits
+                loss = loss + partials.double().sum(dim=0)[0]
+            ctx.save_for_backward(zimg, ztxt, t_prime, bias, *teacher)
+            ctx.step = step
+        ctx.save_g, ctx.alpha, ctx.diag_offset = save_g, alpha, diag_offset
+        return loss.float()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        zimg, ztxt, t_prime, bias, *rest = ctx.saved_tensors
+        n, dev = ztxt.shape[0], zimg.device
+        go = ops._go_scalar(grad_output, dev)
+        t = ops._prep_scalar(t_prime, dev).exp()
+        if ctx.save_g:
+            sums, g = rest
+            # bf16_scale=True: the products stay bf16 (see ops.grad_gemms).
+            dzimg, dztxt = ops.grad_gemms(ops.GBand(g, None, ztxt, None),
+                                          zimg, n, go * t, bf16_scale=True)
+        else:
+            timg, ttxt, teacher_t_prime, teacher_bias = rest
+            parts = []
+
+            def emit(j0, j1, diag_j, g, gt):
+                partials = ops.sigmoid_distill(
+                    zimg, ztxt[j0:j1], t_prime, bias, timg, ttxt[j0:j1],
+                    teacher_t_prime, teacher_bias, ctx.alpha, diag_j, g=g)[0]
+                parts.append(partials.double().sum(dim=0))
+
+            # bf16_scale stays False, also when one band covers the block.
+            # fp32_bands: with soft targets g takes both signs along a row,
+            # the bands' partial dzimg sums cancel, and a bf16 partial would
+            # be rounded at its own size, not at the element's.
+            dzimg, dztxt = ops.band_grad_gemms(
+                zimg, ztxt, ctx.step, emit, go * t,
+                diag_offset=ctx.diag_offset, fp32_bands=True)
+            sums = torch.stack(parts).sum(dim=0)
+        dt = sums[1] * (go * t).double()
+        db = sums[2] * go.double()
+        return (dzimg, dztxt,
+                dt.to(device=t_prime.device,
+                      dtype=t_prime.dtype).reshape(t_prime.shape),
+                db.to(device=bias.device, dtype=bias.dtype).reshape(bias.shape),
+                None, None, None, None, None, None, None, None)
+
+
+def sigmoid_distillation_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
+                              t_prime: torch.Tensor, bias: torch.Tensor,
+                              timg: torch.Tensor, ttxt: torch.Tensor,
+                              teacher_t_prime: torch.Tensor,
+                              teacher_bias: torch.Tensor, alpha: float = 1.0,
+                              diag_offset: Optional[int] = None,
+                              col_chunk: Optional[int] = None,
+                              impl: str = "auto") -> torch.Tensor:
+    """Sum over the ``(b, n)`` block of the sigmoid cross-entropy of every
+    student pair against the teacher's pair probability mixed with the hard
+    label (see the module docstring).  Differentiable in ``zimg``, ``ztxt``,
+    ``t_prime`` and ``bias``; the teacher's arguments get no gradient.
+
+    Args:
+        zimg: ``(b, d)`` student image embeddings (L2-normalized by the
+            caller).
+        ztxt: ``(n, d)`` student text embeddings.
+        t_prime: scalar; the student's temperature is ``exp(t_prime)``.
+        bias: scalar additive logit bias of the student.
+        timg, ttxt: ``(b, d_T)`` / ``(n, d_T)`` teacher embeddings of the same
+            samples; ``d_T`` is independent of ``d``.
+        teacher_t_prime, teacher_bias: the teacher's scalars (tensors or
+            Python numbers), in the student's parametrisation.
+        alpha: weight of the teacher's probability in the target, in
+            ``[0, 1]``; the hard label weighs ``1 − alpha``.
+        diag_offset: column of row 0's hard positive; ``None``: none.
+        col_chunk: columns per kernel pass, bounding the workspace to
+            ``O(b · col_chunk)``; ``None``: the whole block (saved-g when
+            gradients are wanted and the slab stays below 2³² bytes).
+        impl: ``auto`` (``hip`` on GPU when all four embeddings are bf16,
+            ``torch`` elsewhere) | ``hip`` (bf16 on GPU, ``d % 8 == 0`` and
+            ``d_T % 8 == 0``; raises without the built extension or for other
+            dtypes) | ``torch``.
+
+    Returns a 0-d tensor; the caller normalises.
+    """
+    for what, a, c in (("student", zimg, ztxt), ("teacher", timg, ttxt)):
+        if a.dim() != 2 or c.dim() != 2 or a.shape[1] != c.shape[1]:
+            raise ValueError(f"shape mismatch: {what} image "
+                             f"{tuple(a.shape)} text {tuple(c.shape)}")
+    if (timg.shape[0], ttxt.shape[0]) != (zimg.shape[0], ztxt.shape[0]):
+        raise ValueError(
+            f"teacher rows {(timg.shape[0], ttxt.shape[0])} do not pair up "
+            f"with the student's {(zimg.shape[0], ztxt.shape[0])}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
+    if impl == "auto":
+        impl = ("hip" if zimg.is_cuda and all(
+            x.dtype == torch.bfloat16 for x in (zimg, ztxt, timg, ttxt))
+            else "torch")
+    if impl not in ("hip", "torch"):
+        raise ValueError(f"unknown impl {impl!r}")
+    if impl == "torch":
+        return _torch_distill(zimg, ztxt, t_prime, bias, timg, ttxt,
+                              teacher_t_prime, teacher_bias, alpha,
+                              diag_offset, col_chunk)
+    dev = zimg.device
+    want_grad = torch.is_grad_enabled() and any(
+        t.requires_grad for t in (zimg, ztxt, t_prime, bias))
+    return _FusedDistillLoss.apply(
+        zimg, ztxt, t_prime, bias, timg.detach(), ttxt.detach(),
+        ops._prep_scalar(torch.as_tensor(teacher_t_prime), dev),
+        ops._prep_scalar(torch.as_tensor(teacher_bias), dev), alpha,
+        diag_offset, col_chunk, want_grad)
+
+
+class DistributedSigmoidDistillLoss(nn.Module):
+    """All-rank sigmoid distillation loss with module-owned student scalars.
+
+    ``t_prime`` (init ``log 10``) and ``bias`` (init ``−10``) are parameters
+    as in ``DistributedSigmoidLoss``; the teacher's ``teacher_t_prime`` and
+    ``teacher_bias`` are buffers (they move and save with the module and get
+    no gradient).  ``forward`` takes the *local* student and teacher shards,
+    all-gathers the student text shard differentiably and the teacher text
+    shard plainly, evaluates the local ``(b, W·b)`` grid in one call with
+    ``diag_offset = rank·b`` and divides by ``gpu_batch_size``; under DDP
+    gradient averaging that is the single-rank ``sum / (W·b)``.  All-gather
+    strategy only.
+    """
+
+    def __init__(self, gpu_batch_size: int, alpha: float,
+                 teacher_t_prime: float, teacher_bias: float,
+                 col_chunk: Optional[int] = None, impl: str = "auto"):
+        super().__init__()
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
+        self.t_prime = nn.Parameter(torch.tensor(math.log(10.0)))
+        self.bias = nn.Parameter(torch.tensor(-10.0))
+        self.register_buffer("teacher_t_prime",
+                             torch.tensor(float(teacher_t_prime)))
+        self.register_buffer("teacher_bias", torch.tensor(float(teacher_bias)))
+        self.gpu_batch_size = gpu_batch_size
+        self.alpha = float(alpha)
+        self.col_chunk = col_chunk
+        self.impl = impl
+
+    def forward(self, image_embeddings: torch.Tensor,
+                text_embeddings: torch.Tensor,
+                teacher_image_embeddings: torch.Tensor,
+                teacher_text_embeddings: torch.Tensor,
+                group=None) -> torch.Tensor:
+        world, rank = 1, 0
+        if dist.is_available() and dist.is_initialized():
+            world, rank = dist.get_world_size(group), dist.get_rank(group)
+        b_txt = text_embeddings.shape[0]
+        all_txt = all_gather_with_grad(text_embeddings, group=group)
+        all_ttxt = teacher_text_embeddings.detach().contiguous()
+        if world > 1:
+            shard = all_ttxt
+            all_ttxt = shard.new_empty((world * b_txt, shard.shape[1]))
+            dist.all_gather_into_tensor(all_ttxt, shard, group=group)
+        total = sigmoid_distillation_loss(
+            image_embeddings, all_txt, self.t_prime, self.bias,
+            teacher_image_embeddings, all_ttxt, self.teacher_t_prime,
+            self.teacher_bias, alpha=self.alpha, diag_offset=rank * b_txt,
+            col_chunk=self.col_chunk, impl=self.impl)
+        return total / self.gpu_batch_size

@@ -49,6 +49,11 @@ exposes:
   :func:`quantize_mx` and :func:`sigmoid_ids_mx` — OCP MXFP8 operands, one
   e8m0 scale per 32 elements quantised in one pass and applied by the MFMA
   (the pair tile's MX main loop): the ``mxfp8`` policy.
+- distillation: :func:`sigmoid_distill` — the sigmoid loss against a teacher
+  dual encoder's own pair probabilities, mixed with the hard label; a kernel
+  that holds the teacher's and the student's dot-product tiles at once, with
+  the same partials and dL/dlogit slab (``losses/distill.py`` builds the loss,
+  its two backward regimes and the distributed module).
 - sample-ID labels for the softmax loss: :func:`pair_lse_ids` — masked row
   and column log-sum-exp plus each row's and column's positive-logit sum and
   positive count — and :func:`softmax_g_ids` — the dL/dlogit slab with
@@ -222,6 +227,11 @@ _EXPORTS = {
     # (stream, zimg_q, zimg_e8, ztxt_q, ztxt_e8, t', bias, img_ids, txt_ids,
     #  g8, gt8, ws, b, n, d, lde_img, lde_txt, ldg, ldgt, diag, mode)
     "sigmoid_ids_mx": [_P] * 12 + [_I] * 3 + [_L] * 4 + [_I] * 2,
+    "sigmoid_distill_tile_dim": [],
+    # (stream, zimg, ztxt, t', bias, timg, ttxt, t'_T, bias_T, g, ws, b, n, d,
+    #  d_T, ldg, diag, alpha)
+    "sigmoid_distill_bf16": [_P] * 11 + [_I] * 4 + [_L] + [_I]
+                            + [ctypes.c_float],
     "softmax_ids_tile_dim": [],
     # (stream, zimg, ztxt, t', img_ids, txt_ids, row_ws, col_ws, row_lse,
     #  row_pos, row_cnt, col_lse, col_pos, col_cnt, b, n, d, diag, mode)
@@ -876,7 +886,7 @@ class GBand(NamedTuple):
 
 def grad_gemms(bands, zimg: torch.Tensor, n: int, scale: torch.Tensor,
                on_dztxt=None, gt_full: Optional[torch.Tensor] = None,
-               bf16_scale: bool = False):
+               bf16_scale: bool = False, fp32_bands: bool = False):
     """The two gradient GEMMs of every backward regime → ``(dzimg, dztxt)``:
     ``dztxt = scale·gᵀ@zimg`` FIRST, then ``on_dztxt(dztxt)`` (a distributed
     caller's async reduce-scatter overlaps what follows), then
@@ -899,6 +909,13 @@ def grad_gemms(bands, zimg: torch.Tensor, n: int, scale: torch.Tensor,
     recompute path) multiplies by the fp32 scale and then casts.  Products
     headed for the fp32 accumulator, and dequantized e4m3 slabs, always
     take the fp32 scale.
+
+    ``fp32_bands``: a bf16 band's ``g@ztxt`` leaves its GEMM in fp32
+    (``torch.mm(out_dtype=)``) on its way to the fp32 accumulator.  By
+    default it is a bf16 product, rounded at the size of the band's partial
+    sum; where the bands' partial sums are large and cancel (soft targets:
+    ``g`` takes both signs over a row) that rounding exceeds the element's
+    own bf16 ulp several times over.  No effect on a single band.
     """
     b, d = zimg.shape
     single = isinstance(bands, GBand)
@@ -919,6 +936,9 @@ def grad_gemms(bands, zimg: torch.Tensor, n: int, scale: torch.Tensor,
                 # pass, bit-identical to ``out * scale.to(bf16)``.
                 return scale_bf16_(out, scale)
             return out * scale.to(g.dtype)
+        elif fp32_bands and not keep_bf16:
+            return torch.mm(g.T if transpose else g, other,
+                            out_dtype=torch.float32) * s
         return ((g.T if transpose else g) @ other) * s
 
     def dztxt_of(band):
@@ -964,13 +984,13 @@ def band_grad_gemms(zimg: torch.Tensor, ztxt: torch.Tensor, step: int, emit,
                     scale: torch.Tensor, *, diag_offset: Optional[int] = None,
                     g_dtype=torch.bfloat16, with_gt: bool = False,
                     qc: Optional[QuantCache] = None, on_dztxt=None,
-                    bf16_scale: bool = False):
+                    bf16_scale: bool = False, fp32_bands: bool = False):
     """The column-banded recompute backward → ``(dzimg, dztxt)``: per band of
     ``step`` columns, ``emit(j0, j1, diag_j, g, gt)`` writes dL/dlogit of
     columns ``j0:j1`` into the ``(b, j1 − j0)`` slab ``g`` (and its transpose
     into ``gt``, given ``with_gt``; ``None`` otherwise), and
     :func:`grad_gemms` runs the band's two GEMMs (``scale``, ``on_dztxt``,
-    ``bf16_scale`` are its).  ``diag_j`` is ``diag_offset`` shifted to the
+    ``bf16_scale``, ``fp32_bands`` are its).  ``diag_j`` is ``diag_offset`` shifted to the
     band, ``qc`` the per-tensor quantization whose text rows go with each
     band.  ``step >= n`` is one band: a single :class:`GBand`, no fp32
     accumulator."""
@@ -995,7 +1015,8 @@ def band_grad_gemms(zimg: torch.Tensor, ztxt: torch.Tensor, step: int, emit,
             yield GBand(g, gt, ztxt[j0:j1], qc and qc.text_rows(j0, j1))
 
     return grad_gemms(next(bands()) if step == n else bands(), zimg, n, scale,
-                      on_dztxt=on_dztxt, bf16_scale=bf16_scale)
+                      on_dztxt=on_dztxt, bf16_scale=bf16_scale,
+                      fp32_bands=fp32_bands)
 
 
 def scalar_grads(out3: torch.Tensor, go: torch.Tensor, t_eff: torch.Tensor,
@@ -1562,6 +1583,62 @@ def sigmoid_ids_mx(zimg_q: torch.Tensor, zimg_e8: torch.Tensor,
         _DUPLICATES[duplicates]),
         "sigmoid_ids_mx")
     return partials, g, gt
+
+
+def sigmoid_distill(zimg: torch.Tensor, ztxt: torch.Tensor,
+                    t_prime: torch.Tensor, bias: torch.Tensor,
+                    timg: torch.Tensor, ttxt: torch.Tensor,
+                    teacher_t_prime: torch.Tensor, teacher_bias: torch.Tensor,
+                    alpha: float, diag_offset: Optional[int] = None,
+                    g: Optional[torch.Tensor] = None, want_g: bool = True):
+    """Sigmoid distillation loss over the ``(b, n)`` block →
+    ``(partials (tiles, 3) fp32, g | None)``.
+
+    The student pair ``zimg (b, d)`` × ``ztxt (n, d)`` gives ``z_ij =
+    exp(t')·<zimg_i, ztxt_j> + bias``; the teacher pair ``timg (b, d_T)`` ×
+    ``ttxt (n, d_T)`` gives the soft target ``p_ij = σ(exp(t'_T)·<timg_i,
+    ttxt_j> + bias_T)``, mixed with the hard label into ``q_ij = alpha·p_ij +
+    (1 − alpha)·[j == i + diag_offset]`` (``None``: no hard positive).  Per
+    128×128 tile (row-major tile order) ``partials`` holds ``Σ softplus(z) −
+    q·z``, ``Σ g·s`` and ``Σ g`` with ``g = σ(z) − q`` and ``s = (z − bias) /
+    t``; each is reduced in a fixed order, so the result is bitwise
+    reproducible and the same with and without ``g``.  Both grids are
+    evaluated in one kernel and neither is written to memory.
+
+    All four embeddings are bf16 on one device, ``d`` and ``d_T`` multiples
+    of 8 and independent.  ``g``, ``want_g`` and the four scalars (read on the
+    device, no host sync) are as for :func:`sigmoid_ids`; ``alpha`` is a
+    Python number in ``[0, 1]``.  No autograd; the teacher gets no gradient
+    by construction."""
+    zi, zt, b, n, d, dev = _pair_block("sigmoid_distill", zimg, ztxt)
+    ti, tt, b_t, n_t, d_t, dev_t = _pair_block("sigmoid_distill (teacher)",
+                                               timg, ttxt)
+    if (b_t, n_t) != (b, n) or dev_t != dev:
+        raise RuntimeError(
+            f"teacher embeddings must pair up with the student's ({b}, {n}) "
+            f"block on {dev} (got ({b_t}, {n_t}) on {dev_t})")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
+    ldg = n
+    if want_g:
+        g, ldg = _g_view(g, b, n, dev)
+    elif g is not None:
+        raise RuntimeError("g given with want_g=False")
+    lib = _require_lib()
+    tile = lib.sigmoid_distill_tile_dim()
+    scalars = [_prep_scalar(p, dev) for p in (t_prime, bias, teacher_t_prime,
+                                              teacher_bias)]
+    partials = torch.empty((-(-b // tile) * -(-n // tile), 3), device=dev,
+                           dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.sigmoid_distill_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(scalars[0]),
+        _ptr(scalars[1]), _ptr(ti), _ptr(tt), _ptr(scalars[2]),
+        _ptr(scalars[3]), _ptr(g), _ptr(partials), b, n, d, d_t,
+        ctypes.c_longlong(ldg), _diag_arg(diag_offset),
+        ctypes.c_float(alpha)), "sigmoid_distill_bf16")
+    return partials, g
 
 
 def _best_side(name: str, on: bool, best, length: int, device):

@@ -54,6 +54,11 @@ as the reference repo ahmdtaha/distributed_sigmoid_loss:
   probabilities, mixed with the hard label, from a fused HIP kernel that runs
   the teacher's and the student's dot products on each tile and keeps the
   targets in registers; neither ``(b, n)`` grid is built.
+- ``softmax_distillation_loss`` / ``DistributedSoftmaxDistillLoss`` — the
+  softmax / KL form: the student's row and column softmax over the batch
+  pulled towards the teacher's, mixed with the hard InfoNCE label, from a
+  fused HIP kernel pair (one statistics pass for all four log-sum-exps and the
+  cross terms, one dL/dlogit pass); single device or one grid across ranks.
 
 The compute path is PyTorch-ROCm + HIP/CDNA4 kernels + RCCL over xGMI; there
 are no CUDA compatibility layers and no multi-backend dispatch.
@@ -91,7 +96,9 @@ from .losses.softmax_loss import (
 from .losses.id_labels import sigmoid_contrastive_loss_ids
 from .losses.distill import (
     DistributedSigmoidDistillLoss,
+    DistributedSoftmaxDistillLoss,
     sigmoid_distillation_loss,
+    softmax_distillation_loss,
 )
 from .parallel.ring import (
     neighbour_exchange,
@@ -129,6 +136,8 @@ __all__ = [
     "sigmoid_contrastive_loss_ids",
     "DistributedSigmoidDistillLoss",
     "sigmoid_distillation_loss",
+    "DistributedSoftmaxDistillLoss",
+    "softmax_distillation_loss",
     "neighbour_exchange",
     "neighbour_exchange_bidir",
     "neighbour_exchange_with_grad",

@@ -12,7 +12,9 @@ from .softmax_loss import DistributedSoftmaxLoss, softmax_contrastive_loss
 from .id_labels import sigmoid_contrastive_loss_ids
 from .distill import (
     DistributedSigmoidDistillLoss,
+    DistributedSoftmaxDistillLoss,
     sigmoid_distillation_loss,
+    softmax_distillation_loss,
 )
 
 __all__ = ["DistributedSigmoidLoss", "SigLipLoss", "sigmoid_contrastive_loss",
@@ -20,4 +22,5 @@ __all__ = ["DistributedSigmoidLoss", "SigLipLoss", "sigmoid_contrastive_loss",
            "retrieval_ranks", "recall_at_k", "distributed_retrieval_ranks",
            "DistributedSoftmaxLoss", "softmax_contrastive_loss",
            "sigmoid_contrastive_loss_ids", "DistributedSigmoidDistillLoss",
-           "sigmoid_distillation_loss"]
+           "sigmoid_distillation_loss", "DistributedSoftmaxDistillLoss",
+           "softmax_distillation_loss"]

@@ -43,8 +43,13 @@ Per-tile partials are summed in fp64 on the device; nothing syncs with the
 host.  Elsewhere a differentiable torch composite with the same contract runs
 (fp32 compute, fp64 for fp64 inputs) — the CPU path and the tests' reference.
 
+The softmax / KL form (``softmax_distillation_loss``) pulls the student's row
+and column softmax over the batch towards the teacher's — the affinity
+mimicking of TinyCLIP, CLIP-KD's contrastive relational distillation — mixed
+with the hard InfoNCE label; its contract stands above its code below.
+
 Not built: sample-ID masks with soft targets, quantised operands for either
-pair, the softmax / KL form, the ring strategy.
+pair, the ring strategy, teacher LSEs cached across steps.
 """
 
 from __future__ import annotations
@@ -59,6 +64,13 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..parallel.collectives import all_gather_with_grad
+from .retrieval import (
+    _TORCH_ROW_CHUNK,
+    _compute_dtype,
+    _positive_rows,
+    positive_scores,
+)
+from .softmax_loss import _backward, _check_block, _fwd_step, _owner_go
 
 
 def _torch_distill(zimg, ztxt, t_prime, bias, timg, ttxt, teacher_t_prime,
@@ -283,3 +295,332 @@ class DistributedSigmoidDistillLoss(nn.Module):
             self.teacher_bias, alpha=self.alpha, diag_offset=rank * b_txt,
             col_chunk=self.col_chunk, impl=self.impl)
         return total / self.gpu_batch_size
+
+
+# ---------------------------------------------------------------------------
+# The softmax / KL form
+# ---------------------------------------------------------------------------
+#
+# With t = exp(t_prime) and t_T = exp(teacher_t_prime) (no bias: it cancels):
+#
+#     z_ij = t·<zimg_i, ztxt_j>                  v_ij = t_T·<timg_i, ttxt_j>
+#     LS^r_i = log Σ_j exp z_ij                   LS^c_j = log Σ_i exp z_ij
+#     LT^r_i = log Σ_j exp v_ij                   LT^c_j = log Σ_i exp v_ij
+#     P^r_ij = exp(v_ij − LT^r_i)                 P^c_ij = exp(v_ij − LT^c_j)
+#     x^r_i  = Σ_j P^r_ij·(v_ij − z_ij)           x^c_j  = Σ_i P^c_ij·(v_ij − z_ij)
+#
+#     D = Σ_i (LS^r_i − LT^r_i + x^r_i)     (= Σ_i KL(P^r_i ‖ softmax z_i))
+#       + Σ_j (LS^c_j − LT^c_j + x^c_j)
+#     H = softmax_contrastive_loss(zimg, ztxt, t_prime, diag_offset)
+#     total = alpha·D + (1 − alpha)·H
+#
+#     g_ij = rw_i·exp(z_ij − LS^r_i) + cw_j·exp(z_ij − LS^c_j)
+#            − rtw_i·P^r_ij − ctw_j·P^c_ij − [j == i + diag]·(rhw_i + chw_j)
+#     rtw = go·alpha   rhw = go·(1 − alpha)·[row has a positive]   rw = rtw + rhw
+#     dzimg = t·g@ztxt    dztxt = t·gᵀ@zimg    dt' = t·Σ g_ij·s_ij   (s = z/t)
+#
+# Sum form; the teacher side gets no gradient.  x rides on the teacher's LSE:
+# over column chunks and ranks the LSEs fold with logaddexp and x as
+# Σ_c exp(LT_c − LT)·x_c.
+
+
+def _fold_x(lt_a, x_a, lt_b, x_b):
+    """Two shares of a teacher LSE and of the expectation that rides on it →
+    ``(lse, x)`` of their union."""
+    lt = torch.logaddexp(lt_a, lt_b)
+    return lt, torch.exp(lt_a - lt) * x_a + torch.exp(lt_b - lt) * x_b
+
+
+def _torch_pair_distill_stats(zimg, ztxt, t_prime, timg, ttxt,
+                              teacher_t_prime, row_chunk=_TORCH_ROW_CHUNK):
+    """``ops.pair_distill_stats`` as a row-chunked torch composite: holds
+    ``O(row_chunk · n)`` logits of each grid at a time."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    dev, cdt = zimg.device, _compute_dtype(zimg)
+    t = t_prime.detach().to(device=dev, dtype=cdt).exp()
+    tt = teacher_t_prime.detach().to(device=dev, dtype=cdt).exp()
+    zt, ttx = ztxt.detach().to(cdt), ttxt.detach().to(cdt)
+    row = [torch.empty(b, device=dev, dtype=cdt) for _ in range(3)]
+    col_ls = torch.full((n,), -math.inf, device=dev, dtype=cdt)
+    col_lt, col_x = col_ls.clone(), torch.zeros(n, device=dev, dtype=cdt)
+    for r0 in range(0, b, row_chunk):
+        r1 = min(b, r0 + row_chunk)
+        z = (zimg[r0:r1].detach().to(cdt) @ zt.T) * t
+        v = (timg[r0:r1].detach().to(cdt) @ ttx.T) * tt
+
+        def stats(dim):
+            lt = torch.logsumexp(v, dim)
+            x = (torch.exp(v - lt.unsqueeze(dim)) * (v - z)).sum(dim)
+            return torch.logsumexp(z, dim), lt, x
+
+        for out, val in zip(row, stats(1)):
+            out[r0:r1] = val
+        ls_c, lt_c, x_c = stats(0)
+        col_ls = torch.logaddexp(col_ls, ls_c)
+        col_lt, col_x = _fold_x(col_lt, col_x, lt_c, x_c)
+    return ops.PairDistillStats(*row, col_ls, col_lt, col_x)
+
+
+def _torch_softmax_distill_g(zimg, ztxt, t_prime, timg, ttxt,
+                             teacher_t_prime, row, col, diag_offset, g=None,
+                             row_chunk=_TORCH_ROW_CHUNK):
+    """``ops.softmax_distill_g`` as a row-chunked torch composite; ``g`` is
+    in the compute dtype and ``gs_partials`` has one entry."""
+    b, n = zimg.shape[0], ztxt.shape[0]
+    dev, cdt = zimg.device, _compute_dtype(zimg)
+    t = t_prime.detach().to(device=dev, dtype=cdt).exp()
+    tt = teacher_t_prime.detach().to(device=dev, dtype=cdt).exp()
+    zt, ttx = ztxt.detach().to(cdt), ttxt.detach().to(cdt)
+    if g is None:
+        g = torch.empty((b, n), device=dev, dtype=cdt)
+    gs = torch.zeros((), device=dev, dtype=torch.float64)
+    cols = torch.arange(n, device=dev)
+    for r0 in range(0, b, row_chunk):
+        r1 = min(b, r0 + row_chunk)
+        s = zimg[r0:r1].detach().to(cdt) @ zt.T
+        z, v = s * t, (timg[r0:r1].detach().to(cdt) @ ttx.T) * tt
+        gv, hw = torch.zeros_like(z), torch.zeros_like(z)
+        for side, sl in ((row, lambda x: x[r0:r1, None]),
+                         (col, lambda x: x[None, :])):
+            if side is None:
+                continue
+            ls, lt, w, tw, h = (sl(x) for x in side)
+            gv += w * torch.exp(z - ls) - tw * torch.exp(v - lt)
+            hw += h
+        if diag_offset is not None:
+            pos = torch.arange(r0, r1, device=dev) + int(diag_offset)
+            gv -= hw * (cols[None, :] == pos[:, None])
+        g[r0:r1] = gv
+        gs += (gv * s).double().sum()
+    return g, gs.reshape(1)
+
+
+class _SoftmaxDistillLoss(torch.autograd.Function):
+    """Both implementations, in the shape of ``_SoftmaxLoss``: ``hip`` runs
+    the fused kernels and the library gradient GEMMs, ``torch`` the
+    composites above; the chunking, the collectives and the weights are
+    shared."""
+
+    @staticmethod
+    def forward(ctx, zimg, ztxt, t_prime, timg, ttxt, teacher_t_prime, alpha,
+                diag_offset, col_chunk, impl, group):
+        hip = impl == "hip"
+        stats_fn = ops.pair_distill_stats if hip else _torch_pair_distill_stats
+        zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
+        timg, ttxt = timg.contiguous(), ttxt.contiguous()
+        b, n = zimg.shape[0], ztxt.shape[0]
+        row, col_parts = None, []
+        for j0, j1, _ in ops.col_bands(n, _fwd_step(col_chunk, n)):
+            st = stats_fn(zimg, ztxt[j0:j1], t_prime, timg, ttxt[j0:j1],
+                          teacher_t_prime)
+            if row is None:
+                row = st[:3]
+            else:
+                row = (torch.logaddexp(row[0], st[0]),
+                       *_fold_x(row[1], row[2], st[1], st[2]))
+            col_parts.append(torch.stack(st[3:]))
+        col = col_parts[0] if len(col_parts) == 1 else torch.cat(col_parts, 1)
+        own = slice(0, n)
+        if group is not None:
+            # This rank's rows are a share of every column: gather the
+            # shares and fold them in rank order, the same on every rank.
+            world, rank = dist.get_world_size(group), dist.get_rank(group)
+            shares = torch.empty(world * 3 * n, device=col.device,
+                                 dtype=col.dtype)
+            dist.all_gather_into_tensor(shares, col.reshape(-1), group=group)
+            shares = shares.view(world, 3, n)
+            ls = torch.logsumexp(shares[:, 0], dim=0)
+            lt, x = shares[0, 1], shares[0, 2]
+            for q in range(1, world):
+                lt, x = _fold_x(lt, x, shares[q, 1], shares[q, 2])
+            col = torch.stack((ls, lt, x))
+            # Column j belongs to the loss of rank j // b, its text's owner.
+            own = slice(rank * b, (rank + 1) * b)
+        cdt = row[0].dtype
+        kl = ((row[0].double() - row[1].double() + row[2].double()).sum()
+              + (col[0, own].double() - col[1, own].double()
+                 + col[2, own].double()).sum())
+        rows, cols = _positive_rows(b, n, diag_offset, zimg.device)
+        t = t_prime.detach().to(device=zimg.device, dtype=cdt).exp()
+        z_pos = positive_scores(zimg, ztxt, diag_offset)[rows] * t
+        hard = (row[0][rows].double() + col[0][cols].double()
+                - 2.0 * z_pos.double()).sum()
+        total = (alpha * kl + (1.0 - alpha) * hard).to(cdt)
+        ctx.save_for_backward(zimg, ztxt, t_prime, timg, ttxt,
+                              teacher_t_prime, row[0], row[1],
+                              col[0].contiguous(), col[1].contiguous())
+        ctx.alpha, ctx.diag_offset, ctx.col_chunk = alpha, diag_offset, col_chunk
+        ctx.hip, ctx.group = hip, group
+        return total
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (zimg, ztxt, t_prime, timg, ttxt, teacher_t_prime, row_ls, row_lt,
+         col_ls, col_lt) = ctx.saved_tensors
+        b, n = zimg.shape[0], ztxt.shape[0]
+        dev, cdt = zimg.device, row_ls.dtype
+        go = ops._go_scalar(grad_output, dev, cdt)
+        rows, cols = _positive_rows(b, n, ctx.diag_offset, dev)
+        row_tw = (go * ctx.alpha).expand(b).contiguous()
+        row_hw = torch.zeros(b, device=dev, dtype=cdt)
+        row_hw[rows] = go * (1.0 - ctx.alpha)
+        if ctx.group is not None:
+            # Every column has its positive on its owner, whose go it takes.
+            col_go = _owner_go(go, b, ctx.group)
+            col_hw = col_go * (1.0 - ctx.alpha)
+        else:
+            col_go = go.expand(n)
+            col_hw = torch.zeros(n, device=dev, dtype=cdt)
+            col_hw[cols] = go * (1.0 - ctx.alpha)
+        col_tw = (col_go * ctx.alpha).contiguous()
+        row = (row_ls, row_lt, row_tw + row_hw, row_tw, row_hw)
+        col = (col_ls, col_lt, col_tw + col_hw, col_tw, col_hw)
+        t = t_prime.detach().to(device=dev, dtype=cdt).exp()
+        g_fn = ops.softmax_distill_g if ctx.hip else _torch_softmax_distill_g
+        gs_parts = []
+
+        def g_band(j0, j1, diag_j, g, gt):
+            g, gs = g_fn(zimg, ztxt[j0:j1], t_prime, timg, ttxt[j0:j1],
+                         teacher_t_prime, row,
+                         tuple(v[j0:j1].contiguous() for v in col), diag_j,
+                         g=g)
+            gs_parts.append(gs)
+            return g
+
+        # fp32_bands: with soft targets g takes both signs along a row, the
+        # bands' partial dzimg sums cancel, and a bf16 partial would be
+        # rounded at its own size, not at the element's.
+        return _backward(ctx.hip, zimg, ztxt, t_prime, t, ctx.col_chunk,
+                         ctx.diag_offset, g_band, gs_parts, 11,
+                         fp32_bands=True)
+
+
+def softmax_distillation_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
+                              t_prime: torch.Tensor, timg: torch.Tensor,
+                              ttxt: torch.Tensor,
+                              teacher_t_prime: torch.Tensor,
+                              alpha: float = 1.0,
+                              diag_offset: Optional[int] = None,
+                              col_chunk: Optional[int] = None,
+                              impl: str = "auto", group=None) -> torch.Tensor:
+    """Sum over the rows and the columns of the ``(b, n)`` block of the KL
+    divergence of the student's softmax from the teacher's, mixed with the
+    hard softmax contrastive loss: ``alpha·D + (1 − alpha)·H`` (see the
+    contract above).  Differentiable in ``zimg``, ``ztxt`` and ``t_prime``;
+    the teacher's arguments get no gradient.
+
+    ``alpha = 0`` is ``softmax_contrastive_loss``; ``alpha = 1`` is pure
+    distillation — non-negative, and 0 with zero gradient where the
+    student's logits equal the teacher's; ``diag_offset=None`` leaves out
+    the hard part.
+
+    Args:
+        zimg: ``(b, d)`` student image embeddings (L2-normalized by the
+            caller).
+        ztxt: ``(n, d)`` student text embeddings.
+        t_prime: scalar; the student's temperature is ``exp(t_prime)``.
+        timg, ttxt: ``(b, d_T)`` / ``(n, d_T)`` teacher embeddings of the same
+            samples; ``d_T`` is independent of ``d``.
+        teacher_t_prime: the teacher's scalar (tensor or Python number).
+        alpha: weight of the KL part, in ``[0, 1]``; the hard loss weighs
+            ``1 − alpha``.
+        diag_offset: column of row 0's hard positive; ``None``: none.
+        col_chunk: columns per kernel pass (forward statistics and backward
+            g band), bounding the workspace to ``O(b · col_chunk)``; ``None``:
+            the whole block, banded in backward only when the bf16 g slab
+            would reach 2³² bytes.
+        impl: ``auto`` (``hip`` on GPU when all four embeddings are bf16,
+            ``torch`` elsewhere) | ``hip`` (bf16 on GPU, ``d % 8 == 0`` and
+            ``d_T % 8 == 0``; raises without the built extension or for other
+            dtypes) | ``torch``.
+        group: a process group of ``W > 1`` ranks for the one-grid
+            distributed form (``n == W·b``, ``diag_offset == rank·b``):
+            column ``j`` counts for the loss of rank ``j // b``; ``None``:
+            this block alone.
+
+    Returns a 0-d tensor; the caller normalises.
+    """
+    if timg.dim() != 2 or ttxt.dim() != 2 or timg.shape[1] != ttxt.shape[1]:
+        raise ValueError(f"shape mismatch: teacher image {tuple(timg.shape)} "
+                         f"text {tuple(ttxt.shape)}")
+    impl, group, world, rank = _check_block(
+        zimg, ztxt, impl, group, zimg.is_cuda and all(
+            x.dtype == torch.bfloat16 for x in (zimg, ztxt, timg, ttxt)))
+    b, n = zimg.shape[0], ztxt.shape[0]
+    if (timg.shape[0], ttxt.shape[0]) != (b, n):
+        raise ValueError(
+            f"teacher rows {(timg.shape[0], ttxt.shape[0])} do not pair up "
+            f"with the student's {(b, n)}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
+    if group is not None and (n != world * b or diag_offset != rank * b):
+        raise ValueError(
+            f"the distributed form needs n == W·b and diag_offset == "
+            f"rank·b (got b={b}, n={n}, W={world}, rank={rank}, "
+            f"diag_offset={diag_offset})")
+    if not isinstance(teacher_t_prime, torch.Tensor):
+        # A Python number keeps its precision on the fp64 path.
+        teacher_t_prime = torch.tensor(float(teacher_t_prime),
+                                       dtype=torch.float64)
+    return _SoftmaxDistillLoss.apply(
+        zimg, ztxt, t_prime, timg.detach(), ttxt.detach(),
+        teacher_t_prime.detach().to(zimg.device), alpha, diag_offset,
+        col_chunk, impl, group)
+
+
+class DistributedSoftmaxDistillLoss(nn.Module):
+    """All-rank softmax distillation loss with a module-owned, learnable
+    student ``t_prime`` (init ``log(1 / init_temperature)``, clamped in the
+    forward at ``log(max_logit_scale)`` as in ``DistributedSoftmaxLoss``);
+    the teacher's ``teacher_t_prime`` is a buffer.
+
+    ``forward`` takes the *local* student and teacher shards, all-gathers
+    the student text shard differentiably and the teacher text shard
+    plainly, evaluates the ``(b, W·b)`` grid in one call with ``diag_offset =
+    rank·b`` and returns ``total / (2·gpu_batch_size)``; under DDP gradient
+    averaging ``W`` ranks reproduce the single-rank gradients of the global
+    batch.  All-gather strategy only.
+    """
+
+    def __init__(self, gpu_batch_size: int, alpha: float,
+                 teacher_t_prime: float, col_chunk: Optional[int] = None,
+                 impl: str = "auto", init_temperature: float = 0.07,
+                 max_logit_scale: float = 100.0):
+        super().__init__()
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
+        self.t_prime = nn.Parameter(
+            torch.tensor(math.log(1.0 / init_temperature)))
+        self.register_buffer("teacher_t_prime",
+                             torch.tensor(float(teacher_t_prime)))
+        self.gpu_batch_size = gpu_batch_size
+        self.alpha = float(alpha)
+        self.col_chunk = col_chunk
+        self.impl = impl
+        self.max_logit_scale = max_logit_scale
+
+    def forward(self, image_embeddings: torch.Tensor,
+                text_embeddings: torch.Tensor,
+                teacher_image_embeddings: torch.Tensor,
+                teacher_text_embeddings: torch.Tensor,
+                group=None) -> torch.Tensor:
+        world, rank = 1, 0
+        if dist.is_available() and dist.is_initialized():
+            world, rank = dist.get_world_size(group), dist.get_rank(group)
+        b_txt = text_embeddings.shape[0]
+        t_prime = self.t_prime.clamp(max=math.log(self.max_logit_scale))
+        all_txt = all_gather_with_grad(text_embeddings, group=group)
+        all_ttxt = teacher_text_embeddings.detach().contiguous()
+        if world > 1:
+            shard = all_ttxt
+            all_ttxt = shard.new_empty((world * b_txt, shard.shape[1]))
+            dist.all_gather_into_tensor(all_ttxt, shard, group=group)
+            if group is None:
+                group = dist.group.WORLD
+        total = softmax_distillation_loss(
+            image_embeddings, all_txt, t_prime, teacher_image_embeddings,
+            all_ttxt, self.teacher_t_prime, alpha=self.alpha,
+            diag_offset=rank * b_txt, col_chunk=self.col_chunk,
+            impl=self.impl, group=group if world > 1 else None)
+        return total / (2 * self.gpu_batch_size)

@@ -141,18 +141,19 @@ def _owner_go(go, b: int, group):
 
 
 def _backward(hip, zimg, ztxt, t_prime, t, col_chunk, diag_offset, g_band,
-              gs_parts, n_inputs):
-    """What the two Functions' backwards share.  ``g_band(j0, j1, diag_j, g,
+              gs_parts, n_inputs, fp32_bands=False):
+    """What the Functions' backwards share.  ``g_band(j0, j1, diag_j, g,
     gt)`` returns dL/dlogit of columns ``j0:j1`` — written into ``g`` where
     one is handed (the hip path) — and appends the band's ``Σ g·s`` partials
-    to ``gs_parts``.  Returns the ``n_inputs`` gradients: dzimg, dztxt, dt'
-    and ``None`` for the rest."""
+    to ``gs_parts``.  ``fp32_bands`` is :func:`ops.grad_gemms`'s (soft
+    targets).  Returns the ``n_inputs`` gradients: dzimg, dztxt, dt' and
+    ``None`` for the rest."""
     b, n = zimg.shape[0], ztxt.shape[0]
     if hip:
         # The upstream gradient lives in the weights: the scale is t alone.
         dzimg, dztxt = ops.band_grad_gemms(
             zimg, ztxt, ops.g_band_step(b, n, col_chunk), g_band, t,
-            diag_offset=diag_offset)
+            diag_offset=diag_offset, fp32_bands=fp32_bands)
     else:
         cdt = t.dtype
         zi = zimg.to(cdt)

@@ -248,6 +248,13 @@ _EXPORTS = {
     # (stream, zimg, ztxt, img_ids, txt_ids, ws_s, ws_c, out_s, out_c, b, n,
     #  d, diag, k, n_splits)
     "pair_topk_ids_bf16": [_P] * 9 + [_I] * 6,
+    "softmax_distill_tile_dim": [],
+    # (stream, zimg, ztxt, t', timg, ttxt, t'_T, row_ws, col_ws, row_lse_s,
+    #  row_lse_t, row_x, col_lse_s, col_lse_t, col_x, b, n, d, d_T)
+    "softmax_distill_stats_bf16": [_P] * 15 + [_I] * 4,
+    # (stream, zimg, ztxt, t', timg, ttxt, t'_T, 5 row vectors, 5 column
+    #  vectors (lse_s, lse_t, w, tw, hw), g, gs_ws, b, n, d, d_T, ldg, diag)
+    "softmax_distill_g_bf16": [_P] * 19 + [_I] * 4 + [_L] + [_I],
 }
 
 
@@ -1907,6 +1914,142 @@ def softmax_g_ids(zimg: torch.Tensor, ztxt: torch.Tensor,
         _ptr(col_lse), _ptr(col_w), _ptr(col_pw), _ptr(g), _ptr(gs), b, n, d,
         ctypes.c_longlong(ldg), _diag_arg(diag_offset),
         _DUPLICATES[duplicates]), "softmax_ids_g_bf16")
+    return g, gs
+
+
+class PairDistillStats(NamedTuple):
+    """What :func:`pair_distill_stats` returns, fp32 ``(b,)`` / ``(n,)``; a
+    skipped side is three ``None``."""
+    row_lse_s: Optional[torch.Tensor]
+    row_lse_t: Optional[torch.Tensor]
+    row_x: Optional[torch.Tensor]
+    col_lse_s: Optional[torch.Tensor]
+    col_lse_t: Optional[torch.Tensor]
+    col_x: Optional[torch.Tensor]
+
+
+def _distill_block(what: str, zimg, ztxt, t_prime, timg, ttxt,
+                   teacher_t_prime):
+    """Validate the two pairs of a softmax distillation op; returns the
+    contiguous detached embeddings, the two temperatures as device fp32
+    scalars, ``(b, n, d, d_T, device)`` and the tile counts."""
+    zi, zt, b, n, d, dev = _pair_block(what, zimg, ztxt)
+    ti, tt, b_t, n_t, d_t, dev_t = _pair_block(f"{what} (teacher)", timg,
+                                               ttxt)
+    if (b_t, n_t) != (b, n) or dev_t != dev:
+        raise RuntimeError(
+            f"teacher embeddings must pair up with the student's ({b}, {n}) "
+            f"block on {dev} (got ({b_t}, {n_t}) on {dev_t})")
+    tile = _require_lib().softmax_distill_tile_dim()
+    return (zi, zt, _prep_scalar(t_prime, dev), ti, tt,
+            _prep_scalar(torch.as_tensor(teacher_t_prime), dev),
+            (b, n, d, d_t, dev), -(-b // tile), -(-n // tile))
+
+
+def pair_distill_stats(zimg: torch.Tensor, ztxt: torch.Tensor,
+                       t_prime: torch.Tensor, timg: torch.Tensor,
+                       ttxt: torch.Tensor, teacher_t_prime: torch.Tensor,
+                       rows: bool = True,
+                       cols: bool = True) -> PairDistillStats:
+    """What the softmax distillation loss needs of every row and column of
+    the ``(b, n)`` block, from one pass over the student grid ``z =
+    exp(t')·zimg @ ztxtᵀ`` and the teacher grid ``v = exp(t'_T)·timg @
+    ttxtᵀ``, neither of them materialized → :class:`PairDistillStats`:
+    ``lse_s = log Σ exp z``, ``lse_t = log Σ exp v`` and ``x = Σ softmax(v)·
+    (v − z)``, so that ``KL(softmax v ‖ softmax z) = lse_s − lse_t + x``.  A
+    side that is switched off is skipped and returned as ``None``.
+
+    One kernel runs the teacher's and the student's K loops on each 128×128
+    tile and leaves 32-byte records in workspaces from the torch allocator; a
+    second folds them in tile order: no atomics, bitwise reproducible.  All
+    four embeddings are bf16 on one device, ``d`` and ``d_T`` multiples of 8
+    and independent; both temperatures are read on the device (no host sync).
+    Column chunks (``ztxt[j0:j1]``, ``ttxt[j0:j1]``) compose in the caller:
+    ``torch.logaddexp`` of the row LSEs and ``x = Σ_c exp(lse_t,c − lse_t)·
+    x_c``.  No autograd."""
+    zi, zt, tp, ti, tt, tp_t, (b, n, d, d_t, dev), tiles_m, tiles_n = \
+        _distill_block("pair_distill_stats", zimg, ztxt, t_prime, timg, ttxt,
+                       teacher_t_prime)
+    if not rows and not cols:
+        return PairDistillStats(None, None, None, None, None, None)
+    lib = _require_lib()
+
+    def side(on, tiles, length):
+        if not on:
+            return (None,) * 4
+        # 32-byte records (max z, Σ exp, max v, Σ exp, Σ exp·(v − z), pad).
+        return (torch.empty((tiles, length, 8), device=dev,
+                            dtype=torch.float32),) + tuple(
+            torch.empty(length, device=dev, dtype=torch.float32)
+            for _ in range(3))
+
+    row_ws, *row = side(rows, tiles_n, b)
+    col_ws, *col = side(cols, tiles_m, n)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.softmax_distill_stats_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(ti),
+        _ptr(tt), _ptr(tp_t), _ptr(row_ws), _ptr(col_ws),
+        *(_ptr(v) for v in row), *(_ptr(v) for v in col), b, n, d, d_t),
+        "softmax_distill_stats_bf16")
+    return PairDistillStats(*row, *col)
+
+
+_DISTILL_SIDE = ("lse_s", "lse_t", "w", "tw", "hw")
+
+
+def _distill_side(name: str, vecs, length: int, device):
+    """Validate one side of :func:`softmax_distill_g`: ``None``, or the five
+    fp32 vectors ``(lse_s, lse_t, w, tw, hw)``."""
+    if vecs is None:
+        return (None,) * 5
+    if len(vecs) != 5 or any(v is None for v in vecs):
+        raise RuntimeError(
+            f"{name} must be None or the five vectors "
+            f"({', '.join(_DISTILL_SIDE)}) together")
+    for what, v in zip(_DISTILL_SIDE, vecs):
+        if not _vec_ok(v, torch.float32, length, device):
+            raise RuntimeError(
+                f"{name}_{what} must be a contiguous fp32 ({length},) tensor "
+                f"on {device}")
+    return tuple(vecs)
+
+
+def softmax_distill_g(zimg: torch.Tensor, ztxt: torch.Tensor,
+                      t_prime: torch.Tensor, timg: torch.Tensor,
+                      ttxt: torch.Tensor, teacher_t_prime: torch.Tensor,
+                      row, col, diag_offset: Optional[int],
+                      g: Optional[torch.Tensor] = None):
+    """dL/dlogit of the softmax distillation loss over the ``(b, n)`` block
+    → ``(g, gs_partials)``:
+
+    ``g_ij = rw_i·exp(z_ij − LS^r_i) + cw_j·exp(z_ij − LS^c_j) −
+    rtw_i·exp(v_ij − LT^r_i) − ctw_j·exp(v_ij − LT^c_j) − [j == i +
+    diag_offset]·(rhw_i + chw_j)``, bf16, and one fp32 ``Σ g_ij·s_ij`` (``s =
+    z / t``) per 128×128 tile, each reduced in a fixed order (``dt' =
+    t·gs_partials.sum()``).  The teacher's term stays fp32 in registers
+    across the student's K loop.
+
+    ``row`` / ``col`` are ``(lse_s, lse_t, w, tw, hw)``, fp32 ``(b,)`` /
+    ``(n,)``: the student's and the teacher's LSE and the weights of the
+    student's softmax, the teacher's softmax and the hard positive (``w = tw
+    + hw`` for the loss); a side given as ``None`` adds no term.
+    ``diag_offset=None``: no hard positive.  ``g`` as for :func:`softmax_g`.
+    No autograd."""
+    zi, zt, tp, ti, tt, tp_t, (b, n, d, d_t, dev), tiles_m, tiles_n = \
+        _distill_block("softmax_distill_g", zimg, ztxt, t_prime, timg, ttxt,
+                       teacher_t_prime)
+    row = _distill_side("row", row, b, dev)
+    col = _distill_side("col", col, n, dev)
+    g, ldg = _g_view(g, b, n, dev)
+    lib = _require_lib()
+    gs = torch.empty(tiles_m * tiles_n, device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.softmax_distill_g_bf16(
+        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(ti),
+        _ptr(tt), _ptr(tp_t), *(_ptr(v) for v in row),
+        *(_ptr(v) for v in col), _ptr(g), _ptr(gs), b, n, d, d_t,
+        ctypes.c_longlong(ldg), _diag_arg(diag_offset)),
+        "softmax_distill_g_bf16")
     return g, gs
 
 

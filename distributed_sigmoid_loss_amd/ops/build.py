@@ -4,11 +4,12 @@ Compiles ``kernels/siglip_kernels.hip``, ``kernels/wgrad_kernels.hip``,
 ``kernels/rank_kernels.hip``, ``kernels/softmax_kernels.hip``,
 ``kernels/topk_kernels.hip``, ``kernels/idlabel_kernels.hip``,
 ``kernels/softmax_id_kernels.hip``, ``kernels/rank_id_kernels.hip``,
-``kernels/topk_id_kernels.hip``, ``kernels/mx_quant_kernels.hip`` and
-``kernels/distill_kernels.hip`` with hipcc into ``ops/_siglip_hip.so``
+``kernels/topk_id_kernels.hip``, ``kernels/mx_quant_kernels.hip``,
+``kernels/distill_kernels.hip`` and ``kernels/softmax_distill_kernels.hip``
+with hipcc into ``ops/_siglip_hip.so``
 (plain C ABI, loaded via ctypes — no torch C++ ABI coupling, so a single .so
 works across torch builds and travels with the repo snapshot to GPU boxes).
-Eight of them include ``kernels/pair_tile.h`` (the two top-k sources through
+Nine of them include ``kernels/pair_tile.h`` (the two top-k sources through
 ``kernels/topk_list.h``), which sit next to them and need no include flag; the extension is rebuilt
 when a source or any header under ``kernels/`` is newer than the ``.so``.
 
@@ -34,7 +35,8 @@ _SRCS = [os.path.join(_OPS_DIR, "kernels", "siglip_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "rank_id_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "topk_id_kernels.hip"),
          os.path.join(_OPS_DIR, "kernels", "mx_quant_kernels.hip"),
-         os.path.join(_OPS_DIR, "kernels", "distill_kernels.hip")]
+         os.path.join(_OPS_DIR, "kernels", "distill_kernels.hip"),
+         os.path.join(_OPS_DIR, "kernels", "softmax_distill_kernels.hip")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

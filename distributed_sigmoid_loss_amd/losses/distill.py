@@ -48,8 +48,21 @@ and column softmax over the batch towards the teacher's — the affinity
 mimicking of TinyCLIP, CLIP-KD's contrastive relational distillation — mixed
 with the hard InfoNCE label; its contract stands above its code below.
 
-Not built: sample-ID masks with soft targets, quantised operands for either
-pair, the ring strategy, teacher LSEs cached across steps.
+MXFP8 teacher (``teacher_quant="mxfp8"``, both losses and both modules).  The
+teacher gets no gradient and enters no gradient GEMM, so it may be read — and
+stored — as OCP MXFP8: e4m3 elements with one power-of-two scale per 32
+consecutive elements (``ops.quantize_mx``; ``d_T % 32 == 0``).  ``timg`` and
+``ttxt`` are then each a tensor, quantised once per call, or a stored ``(q,
+e8)`` pair, of which no bf16 copy is made on the ``hip`` path: the kernels run
+the teacher's K loop on the MX-scaled MFMA (``ops.sigmoid_distill_mx``,
+``ops.pair_distill_stats_mx``, ``ops.softmax_distill_g_mx``), a band slices
+``q`` and ``e8`` by the rows of ``ztxt``, and the modules gather the teacher
+text shard as two ``uint8`` tensors, half the bytes.  The contract above holds
+with the dequantised teacher ``q·2^(code − 127)`` in place of the tensor;
+``impl="torch"`` dequantises and runs the composites.
+
+Not built: sample-ID masks with soft targets, quantised operands for the
+student pair, the ring strategy, teacher LSEs cached across steps.
 """
 
 from __future__ import annotations
@@ -104,22 +117,103 @@ def _torch_distill(zimg, ztxt, t_prime, bias, timg, ttxt, teacher_t_prime,
     return total
 
 
+TEACHER_QUANTS = ("bf16", "mxfp8")
+
+
+def _is_pair(x) -> bool:
+    return isinstance(x, (tuple, list))
+
+
+def _dequant_mx(q: torch.Tensor, e8: torch.Tensor, dtype) -> torch.Tensor:
+    """``q·2^(code − 127)`` of a ``quantize_mx`` pair: exact in fp32 and
+    fp64."""
+    blocks = q.shape[1] // 32
+    scale = torch.exp2(e8[:, :blocks].to(dtype) - 127.0)
+    return (q.float().to(dtype).view(q.shape[0], blocks, 32)
+            * scale[:, :, None]).reshape(q.shape)
+
+
+def _teacher_operands(timg, ttxt, teacher_quant: str, hip: bool, cdt):
+    """The teacher pair as the implementation reads it.  ``bf16``: the two
+    tensors.  ``mxfp8``: each of ``timg`` / ``ttxt`` is a tensor, quantised
+    here with ``ops.quantize_mx``, or a ``(q, e8)`` pair as it returns one;
+    ``hip`` gets ``(timg_q, timg_e8, ttxt_q, ttxt_e8)`` — no bf16 copy of a
+    stored pair is made — and ``torch`` the dequantised pair in ``cdt``."""
+    if teacher_quant not in TEACHER_QUANTS:
+        raise ValueError(f"unknown teacher_quant {teacher_quant!r}")
+    if teacher_quant == "bf16":
+        if _is_pair(timg) or _is_pair(ttxt):
+            raise ValueError(
+                "a (q, e8) teacher pair needs teacher_quant='mxfp8'")
+        return timg.detach(), ttxt.detach()
+    out = _as_mx_pair("timg", timg) + _as_mx_pair("ttxt", ttxt)
+    if hip:
+        return out
+    return _dequant_mx(out[0], out[1], cdt), _dequant_mx(out[2], out[3], cdt)
+
+
+def _as_mx_pair(what: str, x):
+    """A teacher operand under ``teacher_quant="mxfp8"`` as its ``(q, e8)``
+    pair: a stored pair as it is, a tensor quantised here."""
+    if _is_pair(x) and len(x) != 2:
+        raise ValueError(f"{what} must be a tensor or a (q, e8) pair")
+    shape = tuple(_first(x).shape)
+    if len(shape) != 2 or shape[1] < 32 or shape[1] % 32:
+        raise ValueError(
+            f"teacher_quant='mxfp8' needs d_T % 32 == 0 (got {what} {shape})")
+    q, e8 = x if _is_pair(x) else ops.quantize_mx(x.detach())
+    return q.detach(), e8.detach()
+
+
+def _gather_teacher_text(ttxt, teacher_quant: str, world: int, group):
+    """The module's plain all-gather of the local teacher text shard.  Under
+    ``mxfp8`` the shard is quantised first — rows quantise independently, so
+    the gathered pair is byte for byte the quantised gather — and travels as
+    two ``uint8`` tensors, half the bytes of the bf16 gather."""
+    if teacher_quant not in TEACHER_QUANTS:
+        raise ValueError(f"unknown teacher_quant {teacher_quant!r}")
+
+    def gather(shard):
+        shard = shard.contiguous()
+        if world == 1:
+            return shard
+        out = shard.new_empty((world * shard.shape[0], shard.shape[1]))
+        dist.all_gather_into_tensor(out, shard, group=group)
+        return out
+
+    if teacher_quant == "bf16":
+        if _is_pair(ttxt):
+            raise ValueError(
+                "a (q, e8) teacher pair needs teacher_quant='mxfp8'")
+        return gather(ttxt.detach())
+    q, e8 = _as_mx_pair("ttxt", ttxt)
+    return gather(q.view(torch.uint8)).view(q.dtype), gather(e8)
+
+
+def _teacher_text_rows(teacher, j0: int, j1: int):
+    """``teacher`` (two bf16 tensors, or the four of an MXFP8 pair) with the
+    text side cut to rows ``j0:j1``; row slices stay contiguous."""
+    half = len(teacher) // 2
+    return teacher[:half] + tuple(x[j0:j1] for x in teacher[half:])
+
+
 class _FusedDistillLoss(torch.autograd.Function):
-    """GPU path: ``ops.sigmoid_distill`` plus the library gradient GEMMs, in
-    the saved-g or the band-recompute regime (module docstring)."""
+    """GPU path: ``ops.sigmoid_distill`` (``ops.sigmoid_distill_mx`` for an
+    MXFP8 teacher) plus the library gradient GEMMs, in the saved-g or the
+    band-recompute regime (module docstring)."""
 
     @staticmethod
-    def forward(ctx, zimg, ztxt, t_prime, bias, timg, ttxt, teacher_t_prime,
+    def forward(ctx, zimg, ztxt, t_prime, bias, teacher, teacher_t_prime,
                 teacher_bias, alpha, diag_offset, col_chunk, want_grad):
         zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
-        timg, ttxt = timg.contiguous(), ttxt.contiguous()
+        teacher = tuple(x.contiguous() for x in teacher)
+        op = ops.sigmoid_distill if len(teacher) == 2 else ops.sigmoid_distill_mx
         b, n = zimg.shape[0], ztxt.shape[0]
-        teacher = (timg, ttxt, teacher_t_prime, teacher_bias)
         # want_grad comes from the caller (grad mode is off in here).
         save_g = want_grad and col_chunk is None and b * n * 2 < 2 ** 32
         if save_g:
-            partials, g = ops.sigmoid_distill(
-                zimg, ztxt, t_prime, bias, *teacher, alpha, diag_offset)
+            partials, g = op(zimg, ztxt, t_prime, bias, *teacher,
+                             teacher_t_prime, teacher_bias, alpha, diag_offset)
             sums = partials.double().sum(dim=0)
             ctx.save_for_backward(zimg, ztxt, t_prime, bias, sums, g)
             loss = sums[0]
@@ -128,15 +222,17 @@ class _FusedDistillLoss(torch.autograd.Function):
                        else ops.banded_col_step(b))
             loss = torch.zeros((), device=zimg.device, dtype=torch.float64)
             for j0, j1, diag_j in ops.col_bands(n, step, diag_offset):
-                partials = ops.sigmoid_distill(
-                    zimg, ztxt[j0:j1], t_prime, bias, timg, ttxt[j0:j1],
-                    teacher_t_prime, teacher_bias, alpha, diag_j,
-                    want_g=False)[0]
+                partials = op(
+                    zimg, ztxt[j0:j1], t_prime, bias,
+                    *_teacher_text_rows(teacher, j0, j1), teacher_t_prime,
+                    teacher_bias, alpha, diag_j, want_g=False)[0]
                 # the same reduction as saved-g: one block gives the same bits
                 loss = loss + partials.double().sum(dim=0)[0]
-            ctx.save_for_backward(zimg, ztxt, t_prime, bias, *teacher)
+            ctx.save_for_backward(zimg, ztxt, t_prime, bias, teacher_t_prime,
+                                  teacher_bias, *teacher)
             ctx.step = step
         ctx.save_g, ctx.alpha, ctx.diag_offset = save_g, alpha, diag_offset
+        ctx.op = op
         return loss.float()
 
     @staticmethod
@@ -151,13 +247,15 @@ class _FusedDistillLoss(torch.autograd.Function):
             dzimg, dztxt = ops.grad_gemms(ops.GBand(g, None, ztxt, None),
                                           zimg, n, go * t, bf16_scale=True)
         else:
-            timg, ttxt, teacher_t_prime, teacher_bias = rest
+            teacher_t_prime, teacher_bias, *teacher = rest
+            teacher = tuple(teacher)
             parts = []
 
             def emit(j0, j1, diag_j, g, gt):
-                partials = ops.sigmoid_distill(
-                    zimg, ztxt[j0:j1], t_prime, bias, timg, ttxt[j0:j1],
-                    teacher_t_prime, teacher_bias, ctx.alpha, diag_j, g=g)[0]
+                partials = ctx.op(
+                    zimg, ztxt[j0:j1], t_prime, bias,
+                    *_teacher_text_rows(teacher, j0, j1), teacher_t_prime,
+                    teacher_bias, ctx.alpha, diag_j, g=g)[0]
                 parts.append(partials.double().sum(dim=0))
 
             # bf16_scale stays False, also when one band covers the block.
@@ -174,7 +272,7 @@ class _FusedDistillLoss(torch.autograd.Function):
                 dt.to(device=t_prime.device,
                       dtype=t_prime.dtype).reshape(t_prime.shape),
                 db.to(device=bias.device, dtype=bias.dtype).reshape(bias.shape),
-                None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
 def sigmoid_distillation_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
@@ -184,7 +282,8 @@ def sigmoid_distillation_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
                               teacher_bias: torch.Tensor, alpha: float = 1.0,
                               diag_offset: Optional[int] = None,
                               col_chunk: Optional[int] = None,
-                              impl: str = "auto") -> torch.Tensor:
+                              impl: str = "auto",
+                              teacher_quant: str = "bf16") -> torch.Tensor:
     """Sum over the ``(b, n)`` block of the sigmoid cross-entropy of every
     student pair against the teacher's pair probability mixed with the hard
     label (see the module docstring).  Differentiable in ``zimg``, ``ztxt``,
@@ -210,38 +309,68 @@ def sigmoid_distillation_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
             ``torch`` elsewhere) | ``hip`` (bf16 on GPU, ``d % 8 == 0`` and
             ``d_T % 8 == 0``; raises without the built extension or for other
             dtypes) | ``torch``.
+        teacher_quant: ``bf16`` | ``mxfp8`` — the teacher pair read as OCP
+            MXFP8 (``d_T % 32 == 0``): each of ``timg`` / ``ttxt`` is a
+            tensor, quantised once per call with ``ops.quantize_mx``, or a
+            stored ``(q, e8)`` pair as it returns one.  ``hip`` runs the
+            teacher's K loop on the MX-scaled MFMA; ``torch`` dequantises and
+            runs the composite.  The student pair and all gradients are
+            untouched.
 
     Returns a 0-d tensor; the caller normalises.
     """
-    for what, a, c in (("student", zimg, ztxt), ("teacher", timg, ttxt)):
-        if a.dim() != 2 or c.dim() != 2 or a.shape[1] != c.shape[1]:
-            raise ValueError(f"shape mismatch: {what} image "
-                             f"{tuple(a.shape)} text {tuple(c.shape)}")
-    if (timg.shape[0], ttxt.shape[0]) != (zimg.shape[0], ztxt.shape[0]):
-        raise ValueError(
-            f"teacher rows {(timg.shape[0], ttxt.shape[0])} do not pair up "
-            f"with the student's {(zimg.shape[0], ztxt.shape[0])}")
+    if zimg.dim() != 2 or ztxt.dim() != 2 or zimg.shape[1] != ztxt.shape[1]:
+        raise ValueError(f"shape mismatch: student image "
+                         f"{tuple(zimg.shape)} text {tuple(ztxt.shape)}")
+    _check_teacher(timg, ttxt, zimg.shape[0], ztxt.shape[0])
     alpha = float(alpha)
     if not 0.0 <= alpha <= 1.0:
         raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
     if impl == "auto":
-        impl = ("hip" if zimg.is_cuda and all(
-            x.dtype == torch.bfloat16 for x in (zimg, ztxt, timg, ttxt))
-            else "torch")
+        impl = "hip" if _hip_auto(zimg, ztxt, timg, ttxt) else "torch"
     if impl not in ("hip", "torch"):
         raise ValueError(f"unknown impl {impl!r}")
+    teacher = _teacher_operands(
+        timg, ttxt, teacher_quant, impl == "hip",
+        torch.float64 if zimg.dtype == torch.float64 else torch.float32)
     if impl == "torch":
-        return _torch_distill(zimg, ztxt, t_prime, bias, timg, ttxt,
+        return _torch_distill(zimg, ztxt, t_prime, bias, *teacher,
                               teacher_t_prime, teacher_bias, alpha,
                               diag_offset, col_chunk)
     dev = zimg.device
     want_grad = torch.is_grad_enabled() and any(
         t.requires_grad for t in (zimg, ztxt, t_prime, bias))
     return _FusedDistillLoss.apply(
-        zimg, ztxt, t_prime, bias, timg.detach(), ttxt.detach(),
+        zimg, ztxt, t_prime, bias, teacher,
         ops._prep_scalar(torch.as_tensor(teacher_t_prime), dev),
         ops._prep_scalar(torch.as_tensor(teacher_bias), dev), alpha,
         diag_offset, col_chunk, want_grad)
+
+
+def _first(x):
+    """The tensor that carries a teacher operand's shape, dtype and device:
+    itself, or the ``q`` of a ``(q, e8)`` pair."""
+    return x[0] if _is_pair(x) and len(x) else x
+
+
+def _check_teacher(timg, ttxt, b: int, n: int):
+    """The teacher operands' shapes against the student's ``(b, n)`` block."""
+    ti, tt = _first(timg), _first(ttxt)
+    if ti.dim() != 2 or tt.dim() != 2 or ti.shape[1] != tt.shape[1]:
+        raise ValueError(f"shape mismatch: teacher image {tuple(ti.shape)} "
+                         f"text {tuple(tt.shape)}")
+    if (ti.shape[0], tt.shape[0]) != (b, n):
+        raise ValueError(
+            f"teacher rows {(ti.shape[0], tt.shape[0])} do not pair up "
+            f"with the student's {(b, n)}")
+
+
+def _hip_auto(zimg, ztxt, timg, ttxt) -> bool:
+    """``impl="auto"`` takes ``hip``: bf16 students on a GPU with a teacher in
+    bf16 or stored as ``(q, e8)`` pairs."""
+    return zimg.is_cuda and all(
+        x.dtype == torch.bfloat16 for x in (zimg, ztxt)) and all(
+        _is_pair(x) or x.dtype == torch.bfloat16 for x in (timg, ttxt))
 
 
 class DistributedSigmoidDistillLoss(nn.Module):
@@ -260,10 +389,14 @@ class DistributedSigmoidDistillLoss(nn.Module):
 
     def __init__(self, gpu_batch_size: int, alpha: float,
                  teacher_t_prime: float, teacher_bias: float,
-                 col_chunk: Optional[int] = None, impl: str = "auto"):
+                 col_chunk: Optional[int] = None, impl: str = "auto",
+                 teacher_quant: str = "bf16"):
         super().__init__()
         if not 0.0 <= float(alpha) <= 1.0:
             raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
+        if teacher_quant not in TEACHER_QUANTS:
+            raise ValueError(f"unknown teacher_quant {teacher_quant!r}")
+        self.teacher_quant = teacher_quant
         self.t_prime = nn.Parameter(torch.tensor(math.log(10.0)))
         self.bias = nn.Parameter(torch.tensor(-10.0))
         self.register_buffer("teacher_t_prime",
@@ -284,16 +417,14 @@ class DistributedSigmoidDistillLoss(nn.Module):
             world, rank = dist.get_world_size(group), dist.get_rank(group)
         b_txt = text_embeddings.shape[0]
         all_txt = all_gather_with_grad(text_embeddings, group=group)
-        all_ttxt = teacher_text_embeddings.detach().contiguous()
-        if world > 1:
-            shard = all_ttxt
-            all_ttxt = shard.new_empty((world * b_txt, shard.shape[1]))
-            dist.all_gather_into_tensor(all_ttxt, shard, group=group)
+        all_ttxt = _gather_teacher_text(teacher_text_embeddings,
+                                        self.teacher_quant, world, group)
         total = sigmoid_distillation_loss(
             image_embeddings, all_txt, self.t_prime, self.bias,
             teacher_image_embeddings, all_ttxt, self.teacher_t_prime,
             self.teacher_bias, alpha=self.alpha, diag_offset=rank * b_txt,
-            col_chunk=self.col_chunk, impl=self.impl)
+            col_chunk=self.col_chunk, impl=self.impl,
+            teacher_quant=self.teacher_quant)
         return total / self.gpu_batch_size
 
 
@@ -402,16 +533,20 @@ class _SoftmaxDistillLoss(torch.autograd.Function):
     shared."""
 
     @staticmethod
-    def forward(ctx, zimg, ztxt, t_prime, timg, ttxt, teacher_t_prime, alpha,
+    def forward(ctx, zimg, ztxt, t_prime, teacher, teacher_t_prime, alpha,
                 diag_offset, col_chunk, impl, group):
-        hip = impl == "hip"
-        stats_fn = ops.pair_distill_stats if hip else _torch_pair_distill_stats
+        # teacher: (timg, ttxt), or the four tensors of an MXFP8 pair (hip).
+        hip, mx = impl == "hip", len(teacher) == 4
+        stats_fn = ((ops.pair_distill_stats_mx if mx
+                     else ops.pair_distill_stats) if hip
+                    else _torch_pair_distill_stats)
         zimg, ztxt = zimg.contiguous(), ztxt.contiguous()
-        timg, ttxt = timg.contiguous(), ttxt.contiguous()
+        teacher = tuple(x.contiguous() for x in teacher)
         b, n = zimg.shape[0], ztxt.shape[0]
         row, col_parts = None, []
         for j0, j1, _ in ops.col_bands(n, _fwd_step(col_chunk, n)):
-            st = stats_fn(zimg, ztxt[j0:j1], t_prime, timg, ttxt[j0:j1],
+            st = stats_fn(zimg, ztxt[j0:j1], t_prime,
+                          *_teacher_text_rows(teacher, j0, j1),
                           teacher_t_prime)
             if row is None:
                 row = st[:3]
@@ -446,17 +581,18 @@ class _SoftmaxDistillLoss(torch.autograd.Function):
         hard = (row[0][rows].double() + col[0][cols].double()
                 - 2.0 * z_pos.double()).sum()
         total = (alpha * kl + (1.0 - alpha) * hard).to(cdt)
-        ctx.save_for_backward(zimg, ztxt, t_prime, timg, ttxt,
-                              teacher_t_prime, row[0], row[1],
-                              col[0].contiguous(), col[1].contiguous())
+        ctx.save_for_backward(zimg, ztxt, t_prime, teacher_t_prime, row[0],
+                              row[1], col[0].contiguous(),
+                              col[1].contiguous(), *teacher)
         ctx.alpha, ctx.diag_offset, ctx.col_chunk = alpha, diag_offset, col_chunk
         ctx.hip, ctx.group = hip, group
         return total
 
     @staticmethod
     def backward(ctx, grad_output):
-        (zimg, ztxt, t_prime, timg, ttxt, teacher_t_prime, row_ls, row_lt,
-         col_ls, col_lt) = ctx.saved_tensors
+        (zimg, ztxt, t_prime, teacher_t_prime, row_ls, row_lt, col_ls,
+         col_lt, *teacher) = ctx.saved_tensors
+        teacher = tuple(teacher)
         b, n = zimg.shape[0], ztxt.shape[0]
         dev, cdt = zimg.device, row_ls.dtype
         go = ops._go_scalar(grad_output, dev, cdt)
@@ -476,11 +612,14 @@ class _SoftmaxDistillLoss(torch.autograd.Function):
         row = (row_ls, row_lt, row_tw + row_hw, row_tw, row_hw)
         col = (col_ls, col_lt, col_tw + col_hw, col_tw, col_hw)
         t = t_prime.detach().to(device=dev, dtype=cdt).exp()
-        g_fn = ops.softmax_distill_g if ctx.hip else _torch_softmax_distill_g
+        g_fn = ((ops.softmax_distill_g_mx if len(teacher) == 4
+                 else ops.softmax_distill_g) if ctx.hip
+                else _torch_softmax_distill_g)
         gs_parts = []
 
         def g_band(j0, j1, diag_j, g, gt):
-            g, gs = g_fn(zimg, ztxt[j0:j1], t_prime, timg, ttxt[j0:j1],
+            g, gs = g_fn(zimg, ztxt[j0:j1], t_prime,
+                         *_teacher_text_rows(teacher, j0, j1),
                          teacher_t_prime, row,
                          tuple(v[j0:j1].contiguous() for v in col), diag_j,
                          g=g)
@@ -491,7 +630,7 @@ class _SoftmaxDistillLoss(torch.autograd.Function):
         # bands' partial dzimg sums cancel, and a bf16 partial would be
         # rounded at its own size, not at the element's.
         return _backward(ctx.hip, zimg, ztxt, t_prime, t, ctx.col_chunk,
-                         ctx.diag_offset, g_band, gs_parts, 11,
+                         ctx.diag_offset, g_band, gs_parts, 10,
                          fp32_bands=True)
 
 
@@ -502,7 +641,8 @@ def softmax_distillation_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
                               alpha: float = 1.0,
                               diag_offset: Optional[int] = None,
                               col_chunk: Optional[int] = None,
-                              impl: str = "auto", group=None) -> torch.Tensor:
+                              impl: str = "auto", group=None,
+                              teacher_quant: str = "bf16") -> torch.Tensor:
     """Sum over the rows and the columns of the ``(b, n)`` block of the KL
     divergence of the student's softmax from the teacher's, mixed with the
     hard softmax contrastive loss: ``alpha·D + (1 − alpha)·H`` (see the
@@ -537,20 +677,19 @@ def softmax_distillation_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
             distributed form (``n == W·b``, ``diag_offset == rank·b``):
             column ``j`` counts for the loss of rank ``j // b``; ``None``:
             this block alone.
+        teacher_quant: ``bf16`` | ``mxfp8``, as for
+            ``sigmoid_distillation_loss``: the teacher pair as OCP MXFP8
+            (``d_T % 32 == 0``), tensors quantised per call or stored ``(q,
+            e8)`` pairs.
 
     Returns a 0-d tensor; the caller normalises.
     """
-    if timg.dim() != 2 or ttxt.dim() != 2 or timg.shape[1] != ttxt.shape[1]:
-        raise ValueError(f"shape mismatch: teacher image {tuple(timg.shape)} "
-                         f"text {tuple(ttxt.shape)}")
     impl, group, world, rank = _check_block(
-        zimg, ztxt, impl, group, zimg.is_cuda and all(
-            x.dtype == torch.bfloat16 for x in (zimg, ztxt, timg, ttxt)))
+        zimg, ztxt, impl, group, _hip_auto(zimg, ztxt, timg, ttxt))
     b, n = zimg.shape[0], ztxt.shape[0]
-    if (timg.shape[0], ttxt.shape[0]) != (b, n):
-        raise ValueError(
-            f"teacher rows {(timg.shape[0], ttxt.shape[0])} do not pair up "
-            f"with the student's {(b, n)}")
+    _check_teacher(timg, ttxt, b, n)
+    teacher = _teacher_operands(timg, ttxt, teacher_quant, impl == "hip",
+                                _compute_dtype(zimg))
     alpha = float(alpha)
     if not 0.0 <= alpha <= 1.0:
         raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
@@ -564,7 +703,7 @@ def softmax_distillation_loss(zimg: torch.Tensor, ztxt: torch.Tensor,
         teacher_t_prime = torch.tensor(float(teacher_t_prime),
                                        dtype=torch.float64)
     return _SoftmaxDistillLoss.apply(
-        zimg, ztxt, t_prime, timg.detach(), ttxt.detach(),
+        zimg, ztxt, t_prime, teacher,
         teacher_t_prime.detach().to(zimg.device), alpha, diag_offset,
         col_chunk, impl, group)
 
@@ -586,10 +725,13 @@ class DistributedSoftmaxDistillLoss(nn.Module):
     def __init__(self, gpu_batch_size: int, alpha: float,
                  teacher_t_prime: float, col_chunk: Optional[int] = None,
                  impl: str = "auto", init_temperature: float = 0.07,
-                 max_logit_scale: float = 100.0):
+                 max_logit_scale: float = 100.0, teacher_quant: str = "bf16"):
         super().__init__()
         if not 0.0 <= float(alpha) <= 1.0:
             raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
+        if teacher_quant not in TEACHER_QUANTS:
+            raise ValueError(f"unknown teacher_quant {teacher_quant!r}")
+        self.teacher_quant = teacher_quant
         self.t_prime = nn.Parameter(
             torch.tensor(math.log(1.0 / init_temperature)))
         self.register_buffer("teacher_t_prime",
@@ -611,16 +753,14 @@ class DistributedSoftmaxDistillLoss(nn.Module):
         b_txt = text_embeddings.shape[0]
         t_prime = self.t_prime.clamp(max=math.log(self.max_logit_scale))
         all_txt = all_gather_with_grad(text_embeddings, group=group)
-        all_ttxt = teacher_text_embeddings.detach().contiguous()
-        if world > 1:
-            shard = all_ttxt
-            all_ttxt = shard.new_empty((world * b_txt, shard.shape[1]))
-            dist.all_gather_into_tensor(all_ttxt, shard, group=group)
-            if group is None:
-                group = dist.group.WORLD
+        all_ttxt = _gather_teacher_text(teacher_text_embeddings,
+                                        self.teacher_quant, world, group)
+        if world > 1 and group is None:
+            group = dist.group.WORLD
         total = softmax_distillation_loss(
             image_embeddings, all_txt, t_prime, teacher_image_embeddings,
             all_ttxt, self.teacher_t_prime, alpha=self.alpha,
             diag_offset=rank * b_txt, col_chunk=self.col_chunk,
-            impl=self.impl, group=group if world > 1 else None)
+            impl=self.impl, group=group if world > 1 else None,
+            teacher_quant=self.teacher_quant)
         return total / (2 * self.gpu_batch_size)

@@ -53,7 +53,11 @@ exposes:
   dual encoder's own pair probabilities, mixed with the hard label; a kernel
   that holds the teacher's and the student's dot-product tiles at once, with
   the same partials and dL/dlogit slab (``losses/distill.py`` builds the loss,
-  its two backward regimes and the distributed module).
+  its two backward regimes and the distributed module);
+  :func:`sigmoid_distill_mx`, :func:`pair_distill_stats_mx` and
+  :func:`softmax_distill_g_mx` — the three distillation ops with the teacher
+  pair read as OCP MXFP8 (:func:`quantize_mx`'s pairs) on the MX-scaled MFMA;
+  the student pair stays bf16.
 - sample-ID labels for the softmax loss: :func:`pair_lse_ids` — masked row
   and column log-sum-exp plus each row's and column's positive-logit sum and
   positive count — and :func:`softmax_g_ids` — the dL/dlogit slab with
@@ -255,6 +259,12 @@ _EXPORTS = {
     # (stream, zimg, ztxt, t', timg, ttxt, t'_T, 5 row vectors, 5 column
     #  vectors (lse_s, lse_t, w, tw, hw), g, gs_ws, b, n, d, d_T, ldg, diag)
     "softmax_distill_g_bf16": [_P] * 19 + [_I] * 4 + [_L] + [_I],
+    # The three with an MXFP8 teacher: (timg, ttxt) become (timg_q, timg_e8,
+    # ttxt_q, ttxt_e8) and the scale row stride lde follows d_T.
+    "sigmoid_distill_mxt": [_P] * 13 + [_I] * 4 + [_L] * 2 + [_I]
+                           + [ctypes.c_float],
+    "softmax_distill_stats_mxt": [_P] * 17 + [_I] * 4 + [_L],
+    "softmax_distill_g_mxt": [_P] * 21 + [_I] * 4 + [_L] * 2 + [_I],
 }
 
 
@@ -1510,6 +1520,45 @@ def sigmoid_ids_fp8(zimg_q: torch.Tensor, ztxt_q: torch.Tensor,
     return partials, g, gt
 
 
+def _mx_pair_block(what: str, names, img_q, img_e8, txt_q, txt_e8):
+    """Validate an MXFP8 operand pair of op ``what`` — the layout
+    :func:`quantize_mx` returns, ``names`` the stems of the image and the text
+    operand in messages; returns ``(b, n, d, width, device)``, ``width`` the
+    scale row stride in bytes."""
+    E4M3 = torch.float8_e4m3fn
+    ni, nt = names
+    for name, x, dt in ((f"{ni}_q", img_q, E4M3), (f"{nt}_q", txt_q, E4M3),
+                        (f"{ni}_e8", img_e8, torch.uint8),
+                        (f"{nt}_e8", txt_e8, torch.uint8)):
+        if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != dt
+                or not x.is_cuda or not x.is_contiguous()):
+            raise RuntimeError(
+                f"{what}: {name} must be a contiguous {dt} 2-D GPU "
+                f"tensor (got {getattr(x, 'dtype', type(x))} "
+                f"{tuple(getattr(x, 'shape', ()))} on "
+                f"{getattr(x, 'device', None)})")
+    (b, d), n, dev = img_q.shape, txt_q.shape[0], img_q.device
+    if txt_q.shape[1] != d or any(
+            x.device != dev for x in (img_e8, txt_q, txt_e8)):
+        raise RuntimeError(
+            f"expected (b, d) and (n, d) embeddings on one device, got "
+            f"{tuple(img_q.shape)} and {tuple(txt_q.shape)}")
+    if b < 1 or n < 1:
+        raise RuntimeError(f"{what} needs a non-empty block")
+    if d % 32 != 0:
+        raise RuntimeError(
+            f"emb dim must be a multiple of 32 for mxfp8 (got {d})")
+    width = 4 * (-(-d // 128))
+    for name, e8, rows in ((f"{ni}_e8", img_e8, b), (f"{nt}_e8", txt_e8, n)):
+        if tuple(e8.shape) != (rows, width):
+            raise RuntimeError(
+                f"{what}: {name} must have shape ({rows}, {width}) "
+                f"(got {tuple(e8.shape)})")
+        if e8.data_ptr() % 4 != 0:
+            raise RuntimeError(f"{what}: {name} must be 4-byte aligned")
+    return b, n, d, width, dev
+
+
 def sigmoid_ids_mx(zimg_q: torch.Tensor, zimg_e8: torch.Tensor,
                    ztxt_q: torch.Tensor, ztxt_e8: torch.Tensor,
                    t_prime: torch.Tensor, bias: torch.Tensor,
@@ -1534,36 +1583,8 @@ def sigmoid_ids_mx(zimg_q: torch.Tensor, zimg_e8: torch.Tensor,
     that function's bit for bit.  Every failure raises before any launch.  No
     autograd."""
     E4M3 = torch.float8_e4m3fn
-    for what, x, dt in (("zimg_q", zimg_q, E4M3), ("ztxt_q", ztxt_q, E4M3),
-                        ("zimg_e8", zimg_e8, torch.uint8),
-                        ("ztxt_e8", ztxt_e8, torch.uint8)):
-        if (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != dt
-                or not x.is_cuda or not x.is_contiguous()):
-            raise RuntimeError(
-                f"sigmoid_ids_mx: {what} must be a contiguous {dt} 2-D GPU "
-                f"tensor (got {getattr(x, 'dtype', type(x))} "
-                f"{tuple(getattr(x, 'shape', ()))} on "
-                f"{getattr(x, 'device', None)})")
-    (b, d), n, dev = zimg_q.shape, ztxt_q.shape[0], zimg_q.device
-    if ztxt_q.shape[1] != d or any(
-            x.device != dev for x in (zimg_e8, ztxt_q, ztxt_e8)):
-        raise RuntimeError(
-            f"expected (b, d) and (n, d) embeddings on one device, got "
-            f"{tuple(zimg_q.shape)} and {tuple(ztxt_q.shape)}")
-    if b < 1 or n < 1:
-        raise RuntimeError("sigmoid_ids_mx needs a non-empty block")
-    if d % 32 != 0:
-        raise RuntimeError(
-            f"emb dim must be a multiple of 32 for mxfp8 (got {d})")
-    width = 4 * (-(-d // 128))
-    for what, e8, rows in (("zimg_e8", zimg_e8, b), ("ztxt_e8", ztxt_e8, n)):
-        if tuple(e8.shape) != (rows, width):
-            raise RuntimeError(
-                f"sigmoid_ids_mx: {what} must have shape ({rows}, {width}) "
-                f"(got {tuple(e8.shape)})")
-        if e8.data_ptr() % 4 != 0:
-            raise RuntimeError(
-                f"sigmoid_ids_mx: {what} must be 4-byte aligned")
+    b, n, d, width, dev = _mx_pair_block(
+        "sigmoid_ids_mx", ("zimg", "ztxt"), zimg_q, zimg_e8, ztxt_q, ztxt_e8)
     _check_id_labels(duplicates, img_ids, txt_ids, b, n, dev)
     ldg, ldgt = n, b
     if not want_g:
@@ -1617,13 +1638,38 @@ def sigmoid_distill(zimg: torch.Tensor, ztxt: torch.Tensor,
     device, no host sync) are as for :func:`sigmoid_ids`; ``alpha`` is a
     Python number in ``[0, 1]``.  No autograd; the teacher gets no gradient
     by construction."""
-    zi, zt, b, n, d, dev = _pair_block("sigmoid_distill", zimg, ztxt)
-    ti, tt, b_t, n_t, d_t, dev_t = _pair_block("sigmoid_distill (teacher)",
-                                               timg, ttxt)
+    return _sigmoid_distill("sigmoid_distill", zimg, ztxt, t_prime, bias,
+                            (timg, ttxt), teacher_t_prime, teacher_bias,
+                            alpha, diag_offset, g, want_g)
+
+
+def _teacher_block(what: str, teacher, b: int, n: int, dev):
+    """Validate the teacher pair of a distillation op against the student's
+    ``(b, n)`` block on ``dev``.  ``teacher`` is ``(timg, ttxt)`` in bf16 or
+    ``(timg_q, timg_e8, ttxt_q, ttxt_e8)`` in MXFP8; returns the tensors the
+    kernel reads, ``d_T`` and the scale row stride (``None`` for bf16)."""
+    if len(teacher) == 2:
+        ti, tt, b_t, n_t, d_t, dev_t = _pair_block(f"{what} (teacher)",
+                                                   *teacher)
+        tensors, lde = (ti, tt), None
+    else:
+        b_t, n_t, d_t, lde, dev_t = _mx_pair_block(what, ("timg", "ttxt"),
+                                                   *teacher)
+        tensors = tuple(teacher)
     if (b_t, n_t) != (b, n) or dev_t != dev:
         raise RuntimeError(
             f"teacher embeddings must pair up with the student's ({b}, {n}) "
             f"block on {dev} (got ({b_t}, {n_t}) on {dev_t})")
+    return tensors, d_t, lde
+
+
+def _sigmoid_distill(what, zimg, ztxt, t_prime, bias, teacher,
+                     teacher_t_prime, teacher_bias, alpha, diag_offset, g,
+                     want_g):
+    """:func:`sigmoid_distill` and :func:`sigmoid_distill_mx`: one validation,
+    the entry picked by the teacher's format."""
+    zi, zt, b, n, d, dev = _pair_block(what, zimg, ztxt)
+    t_ops, d_t, lde = _teacher_block(what, teacher, b, n, dev)
     alpha = float(alpha)
     if not 0.0 <= alpha <= 1.0:
         raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
@@ -1639,13 +1685,42 @@ def sigmoid_distill(zimg: torch.Tensor, ztxt: torch.Tensor,
     partials = torch.empty((-(-b // tile) * -(-n // tile), 3), device=dev,
                            dtype=torch.float32)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib.sigmoid_distill_bf16(
-        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(scalars[0]),
-        _ptr(scalars[1]), _ptr(ti), _ptr(tt), _ptr(scalars[2]),
-        _ptr(scalars[3]), _ptr(g), _ptr(partials), b, n, d, d_t,
-        ctypes.c_longlong(ldg), _diag_arg(diag_offset),
-        ctypes.c_float(alpha)), "sigmoid_distill_bf16")
+    head = (ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(scalars[0]),
+            _ptr(scalars[1]), *(_ptr(x) for x in t_ops), _ptr(scalars[2]),
+            _ptr(scalars[3]), _ptr(g), _ptr(partials), b, n, d, d_t)
+    tail = (ctypes.c_longlong(ldg), _diag_arg(diag_offset),
+            ctypes.c_float(alpha))
+    if lde is None:
+        _check(lib.sigmoid_distill_bf16(*head, *tail), "sigmoid_distill_bf16")
+    else:
+        _check(lib.sigmoid_distill_mxt(*head, ctypes.c_longlong(lde), *tail),
+               "sigmoid_distill_mxt")
     return partials, g
+
+
+def sigmoid_distill_mx(zimg: torch.Tensor, ztxt: torch.Tensor,
+                       t_prime: torch.Tensor, bias: torch.Tensor,
+                       timg_q: torch.Tensor, timg_e8: torch.Tensor,
+                       ttxt_q: torch.Tensor, ttxt_e8: torch.Tensor,
+                       teacher_t_prime: torch.Tensor,
+                       teacher_bias: torch.Tensor, alpha: float,
+                       diag_offset: Optional[int] = None,
+                       g: Optional[torch.Tensor] = None, want_g: bool = True):
+    """:func:`sigmoid_distill` with an MXFP8 teacher: ``timg_q (b, d_T)`` /
+    ``ttxt_q (n, d_T)`` ``float8_e4m3fn`` and ``timg_e8 (b, w)`` / ``ttxt_e8
+    (n, w)`` ``uint8``, ``w = 4·ceil(d_T / 128)``, the contiguous pairs
+    :func:`quantize_mx` returns (``d_T % 32 == 0``; a row slice of a pair
+    qualifies).  The teacher's K loop runs on the MX-scaled MFMA, which applies
+    the e8m0 scales, so its dot is the true dot of the dequantised values
+    ``q·2^(code − 127)`` and ``teacher_t_prime`` / ``teacher_bias`` are passed
+    unchanged.  The student pair stays bf16 and everything else — partials,
+    ``g``, ``want_g``, the scalars — is :func:`sigmoid_distill`'s; where the
+    dequantised teacher's dots are exact in fp32 the results are its bits.
+    Every failure raises before any launch.  No autograd."""
+    return _sigmoid_distill("sigmoid_distill_mx", zimg, ztxt, t_prime, bias,
+                            (timg_q, timg_e8, ttxt_q, ttxt_e8),
+                            teacher_t_prime, teacher_bias, alpha, diag_offset,
+                            g, want_g)
 
 
 def _best_side(name: str, on: bool, best, length: int, device):
@@ -1928,22 +2003,18 @@ class PairDistillStats(NamedTuple):
     col_x: Optional[torch.Tensor]
 
 
-def _distill_block(what: str, zimg, ztxt, t_prime, timg, ttxt,
-                   teacher_t_prime):
-    """Validate the two pairs of a softmax distillation op; returns the
-    contiguous detached embeddings, the two temperatures as device fp32
-    scalars, ``(b, n, d, d_T, device)`` and the tile counts."""
+def _distill_block(what: str, zimg, ztxt, t_prime, teacher, teacher_t_prime):
+    """Validate the two pairs of a softmax distillation op (``teacher`` as
+    for :func:`_teacher_block`); returns the contiguous detached student
+    embeddings, the two temperatures as device fp32 scalars, the teacher's
+    tensors, ``(b, n, d, d_T, device)``, the tile counts and the teacher's
+    scale row stride (``None``: a bf16 teacher)."""
     zi, zt, b, n, d, dev = _pair_block(what, zimg, ztxt)
-    ti, tt, b_t, n_t, d_t, dev_t = _pair_block(f"{what} (teacher)", timg,
-                                               ttxt)
-    if (b_t, n_t) != (b, n) or dev_t != dev:
-        raise RuntimeError(
-            f"teacher embeddings must pair up with the student's ({b}, {n}) "
-            f"block on {dev} (got ({b_t}, {n_t}) on {dev_t})")
+    t_ops, d_t, lde = _teacher_block(what, teacher, b, n, dev)
     tile = _require_lib().softmax_distill_tile_dim()
-    return (zi, zt, _prep_scalar(t_prime, dev), ti, tt,
+    return (zi, zt, _prep_scalar(t_prime, dev), t_ops,
             _prep_scalar(torch.as_tensor(teacher_t_prime), dev),
-            (b, n, d, d_t, dev), -(-b // tile), -(-n // tile))
+            (b, n, d, d_t, dev), -(-b // tile), -(-n // tile), lde)
 
 
 def pair_distill_stats(zimg: torch.Tensor, ztxt: torch.Tensor,
@@ -1967,9 +2038,30 @@ def pair_distill_stats(zimg: torch.Tensor, ztxt: torch.Tensor,
     Column chunks (``ztxt[j0:j1]``, ``ttxt[j0:j1]``) compose in the caller:
     ``torch.logaddexp`` of the row LSEs and ``x = Σ_c exp(lse_t,c − lse_t)·
     x_c``.  No autograd."""
-    zi, zt, tp, ti, tt, tp_t, (b, n, d, d_t, dev), tiles_m, tiles_n = \
-        _distill_block("pair_distill_stats", zimg, ztxt, t_prime, timg, ttxt,
-                       teacher_t_prime)
+    return _pair_distill_stats("pair_distill_stats", zimg, ztxt, t_prime,
+                               (timg, ttxt), teacher_t_prime, rows, cols)
+
+
+def pair_distill_stats_mx(zimg: torch.Tensor, ztxt: torch.Tensor,
+                          t_prime: torch.Tensor, timg_q: torch.Tensor,
+                          timg_e8: torch.Tensor, ttxt_q: torch.Tensor,
+                          ttxt_e8: torch.Tensor,
+                          teacher_t_prime: torch.Tensor, rows: bool = True,
+                          cols: bool = True) -> PairDistillStats:
+    """:func:`pair_distill_stats` with an MXFP8 teacher — the operands and
+    the contract of :func:`sigmoid_distill_mx`: ``v`` is ``exp(t'_T)`` times
+    the true dot of the dequantised values, ``teacher_t_prime`` is passed
+    unchanged, the student pair stays bf16.  Every failure raises before any
+    launch.  No autograd."""
+    return _pair_distill_stats("pair_distill_stats_mx", zimg, ztxt, t_prime,
+                               (timg_q, timg_e8, ttxt_q, ttxt_e8),
+                               teacher_t_prime, rows, cols)
+
+
+def _pair_distill_stats(what, zimg, ztxt, t_prime, teacher, teacher_t_prime,
+                        rows, cols):
+    zi, zt, tp, t_ops, tp_t, (b, n, d, d_t, dev), tiles_m, tiles_n, lde = \
+        _distill_block(what, zimg, ztxt, t_prime, teacher, teacher_t_prime)
     if not rows and not cols:
         return PairDistillStats(None, None, None, None, None, None)
     lib = _require_lib()
@@ -1986,11 +2078,15 @@ def pair_distill_stats(zimg: torch.Tensor, ztxt: torch.Tensor,
     row_ws, *row = side(rows, tiles_n, b)
     col_ws, *col = side(cols, tiles_m, n)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib.softmax_distill_stats_bf16(
-        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(ti),
-        _ptr(tt), _ptr(tp_t), _ptr(row_ws), _ptr(col_ws),
-        *(_ptr(v) for v in row), *(_ptr(v) for v in col), b, n, d, d_t),
-        "softmax_distill_stats_bf16")
+    args = (ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp),
+            *(_ptr(x) for x in t_ops), _ptr(tp_t), _ptr(row_ws), _ptr(col_ws),
+            *(_ptr(v) for v in row), *(_ptr(v) for v in col), b, n, d, d_t)
+    if lde is None:
+        _check(lib.softmax_distill_stats_bf16(*args),
+               "softmax_distill_stats_bf16")
+    else:
+        _check(lib.softmax_distill_stats_mxt(*args, ctypes.c_longlong(lde)),
+               "softmax_distill_stats_mxt")
     return PairDistillStats(*row, *col)
 
 
@@ -2035,21 +2131,46 @@ def softmax_distill_g(zimg: torch.Tensor, ztxt: torch.Tensor,
     + hw`` for the loss); a side given as ``None`` adds no term.
     ``diag_offset=None``: no hard positive.  ``g`` as for :func:`softmax_g`.
     No autograd."""
-    zi, zt, tp, ti, tt, tp_t, (b, n, d, d_t, dev), tiles_m, tiles_n = \
-        _distill_block("softmax_distill_g", zimg, ztxt, t_prime, timg, ttxt,
-                       teacher_t_prime)
+    return _softmax_distill_g("softmax_distill_g", zimg, ztxt, t_prime,
+                              (timg, ttxt), teacher_t_prime, row, col,
+                              diag_offset, g)
+
+
+def softmax_distill_g_mx(zimg: torch.Tensor, ztxt: torch.Tensor,
+                         t_prime: torch.Tensor, timg_q: torch.Tensor,
+                         timg_e8: torch.Tensor, ttxt_q: torch.Tensor,
+                         ttxt_e8: torch.Tensor,
+                         teacher_t_prime: torch.Tensor, row, col,
+                         diag_offset: Optional[int],
+                         g: Optional[torch.Tensor] = None):
+    """:func:`softmax_distill_g` with an MXFP8 teacher — the operands and the
+    contract of :func:`sigmoid_distill_mx`.  Every failure raises before any
+    launch.  No autograd."""
+    return _softmax_distill_g("softmax_distill_g_mx", zimg, ztxt, t_prime,
+                              (timg_q, timg_e8, ttxt_q, ttxt_e8),
+                              teacher_t_prime, row, col, diag_offset, g)
+
+
+def _softmax_distill_g(what, zimg, ztxt, t_prime, teacher, teacher_t_prime,
+                       row, col, diag_offset, g):
+    zi, zt, tp, t_ops, tp_t, (b, n, d, d_t, dev), tiles_m, tiles_n, lde = \
+        _distill_block(what, zimg, ztxt, t_prime, teacher, teacher_t_prime)
     row = _distill_side("row", row, b, dev)
     col = _distill_side("col", col, n, dev)
     g, ldg = _g_view(g, b, n, dev)
     lib = _require_lib()
     gs = torch.empty(tiles_m * tiles_n, device=dev, dtype=torch.float32)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib.softmax_distill_g_bf16(
-        ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp), _ptr(ti),
-        _ptr(tt), _ptr(tp_t), *(_ptr(v) for v in row),
-        *(_ptr(v) for v in col), _ptr(g), _ptr(gs), b, n, d, d_t,
-        ctypes.c_longlong(ldg), _diag_arg(diag_offset)),
-        "softmax_distill_g_bf16")
+    head = (ctypes.c_void_p(stream), _ptr(zi), _ptr(zt), _ptr(tp),
+            *(_ptr(x) for x in t_ops), _ptr(tp_t), *(_ptr(v) for v in row),
+            *(_ptr(v) for v in col), _ptr(g), _ptr(gs), b, n, d, d_t)
+    tail = (ctypes.c_longlong(ldg), _diag_arg(diag_offset))
+    if lde is None:
+        _check(lib.softmax_distill_g_bf16(*head, *tail),
+               "softmax_distill_g_bf16")
+    else:
+        _check(lib.softmax_distill_g_mxt(*head, ctypes.c_longlong(lde),
+                                         *tail), "softmax_distill_g_mxt")
     return g, gs
 
 

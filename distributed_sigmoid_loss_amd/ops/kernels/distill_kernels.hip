@@ -30,6 +30,20 @@
 // per CU (__launch_bounds__(256, 2): 256 VGPRs + AGPRs per lane), which hide
 // each other's conversion and epilogue.
 //
+// MXFP8 teacher (sigmoid_distill_kernel<WRITE_G, mx_e4m3>).  The teacher gets
+// no gradient and enters no gradient GEMM, so it may be stored as e4m3 bytes
+// with one e8m0 scale per 32 k (ops.quantize_mx).  Its K loop is then
+// pair_tile.h's MX main loop — half the K-steps and barriers, half the bytes
+// per k, v_mfma_scale_f32_16x16x128_f8f6f4 applying the scales, so u is the
+// true dot of the dequantised values and t'_T, bias_T are unchanged — and
+// everything from the target conversion on is the same code.  During that
+// loop only the 64 teacher accumulators are live, so its resident text
+// fragments and scales have room.  LDS is MX_LDS_BYTES (66 KiB; two
+// workgroups are 132 of 160 KiB): the scale area lies above everything the
+// student loop and the epilogue staging use, and the MX loop ends on a
+// barrier, so the student's first stage overwrites the teacher's last slabs
+// with no barrier added.
+//
 // The hard label is folded into q at the conversion — q = fma(alpha, p, hard)
 // with hard = 1 − alpha on the lane's positive column and 0 elsewhere — so
 // the epilogue knows nothing of positions, and alpha = 0 gives q = [j == i +
@@ -49,6 +63,8 @@
 
 #include "pair_tile.h"
 
+#include <type_traits>
+
 namespace {
 
 // 4 waves × 3 partials above the g staging.
@@ -61,15 +77,21 @@ __device__ __forceinline__ float sigmoid_f32(float x) {
   return (x >= 0.f ? 1.f : e) * __builtin_amdgcn_rcpf(1.f + e);
 }
 
-template <bool WRITE_G>
+// TOP is the teacher's operand element: __bf16, or mx_e4m3 with the block
+// scales in timg_e8 / ttxt_e8, rows lde bytes apart (unused for __bf16).
+template <bool WRITE_G, typename TOP = __bf16>
 __launch_bounds__(NTHREADS, 2) __global__ void sigmoid_distill_kernel(
     const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt,
     const float* __restrict__ tprime, const float* __restrict__ bias,
-    const __bf16* __restrict__ timg, const __bf16* __restrict__ ttxt,
+    const TOP* __restrict__ timg, const TOP* __restrict__ ttxt,
     const float* __restrict__ tprime_t, const float* __restrict__ bias_t,
     __bf16* __restrict__ g, float* __restrict__ ws, int b, int n, int d,
-    int d_t, long long ldg, int diag, float alpha, int tiles_m, int tiles_n) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
+    int d_t, long long ldg, int diag, float alpha, int tiles_m, int tiles_n,
+    const unsigned char* __restrict__ timg_e8,
+    const unsigned char* __restrict__ ttxt_e8, int lde) {
+  constexpr bool MX_T = std::is_same<TOP, mx_e4m3>::value;
+  __shared__ __attribute__((aligned(16))) unsigned char
+      lds[MX_T ? MX_LDS_BYTES : 2 * BUF_BYTES];
   const TilePos tp = tile_of_block(tiles_m, tiles_n);
   const int m0 = tp.tm * BM, n0 = tp.tn * BN;
 
@@ -81,7 +103,12 @@ __launch_bounds__(NTHREADS, 2) __global__ void sigmoid_distill_kernel(
 
   // Teacher: dots, then the targets in place.
   f32x4 q[4][4];
-  pair_tile_dots<true>(timg, ttxt, b, n, d_t, m0, n0, lds, q);
+  if constexpr (MX_T)
+    pair_tile_dots_mx<true>((const unsigned char*)timg, timg_e8,
+                            (const unsigned char*)ttxt, ttxt_e8, b, n, d_t,
+                            lde, m0, n0, lds, q);
+  else
+    pair_tile_dots<true>(timg, ttxt, b, n, d_t, m0, n0, lds, q);
   {
     const float tt = expf(tprime_t[0]);
     const float bt = bias_t[0];
@@ -212,7 +239,51 @@ int sigmoid_distill_bf16(uintptr_t stream, const void* zimg, const void* ztxt,
                      (const float*)bias, (const __bf16*)timg,
                      (const __bf16*)ttxt, (const float*)tprime_t,
                      (const float*)bias_t, (__bf16*)g, (float*)ws, b, n, d,
-                     d_t, ldg, diag, alpha, tiles_m, tiles_n);
+                     d_t, ldg, diag, alpha, tiles_m, tiles_n,
+                     (const unsigned char*)nullptr,
+                     (const unsigned char*)nullptr, 0);
+  return (int)hipGetLastError();
+}
+
+// The same loss with an MXFP8 teacher pair: timg_q (b, d_t), ttxt_q (n, d_t)
+// OCP e4m3fn bytes, row-major contiguous, d_t a multiple of 32; timg_e8 (b
+// rows), ttxt_e8 (n rows) their e8m0 block scales, byte kb of a row for
+// elements 32·kb … +31, 4-byte aligned with rows lde bytes apart, exactly
+// 4·ceil(d_t / 128).  The teacher's dot is the true dot of the dequantised
+// values (the MFMA applies the scales), so tprime_t and bias_t are those of
+// sigmoid_distill_bf16.  The student pair, ws, g and every other check as
+// there.  Returns non-zero, launching nothing, on anything unsupported.
+int sigmoid_distill_mxt(uintptr_t stream, const void* zimg, const void* ztxt,
+                        const void* tprime, const void* bias,
+                        const void* timg_q, const void* timg_e8,
+                        const void* ttxt_q, const void* ttxt_e8,
+                        const void* tprime_t, const void* bias_t, void* g,
+                        void* ws, int b, int n, int d, int d_t, long long lde,
+                        long long ldg, int diag, float alpha) {
+  if (!pair_dims_ok(zimg, ztxt, b, n, d) ||
+      !pair_dims_ok_mx(timg_q, timg_e8, ttxt_q, ttxt_e8, b, n, d_t, lde,
+                       lde) ||
+      tprime == nullptr || bias == nullptr || tprime_t == nullptr ||
+      bias_t == nullptr || ws == nullptr || !(alpha >= 0.f && alpha <= 1.f))
+    return (int)hipErrorInvalidValue;
+  if (((uintptr_t)tprime | (uintptr_t)bias | (uintptr_t)tprime_t |
+       (uintptr_t)bias_t | (uintptr_t)ws) % 4 != 0 ||
+      (uintptr_t)g % 2 != 0)
+    return (int)hipErrorInvalidValue;
+  if (g != nullptr && ldg < n) return (int)hipErrorInvalidValue;
+  const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
+  if (!pair_grid_ok(tiles_m, tiles_n)) return (int)hipErrorInvalidValue;
+  const auto kernel = g != nullptr ? sigmoid_distill_kernel<true, mx_e4m3>
+                                   : sigmoid_distill_kernel<false, mx_e4m3>;
+  hipLaunchKernelGGL(kernel, dim3(tiles_m * tiles_n), dim3(NTHREADS), 0,
+                     (hipStream_t)stream, (const __bf16*)zimg,
+                     (const __bf16*)ztxt, (const float*)tprime,
+                     (const float*)bias, (const mx_e4m3*)timg_q,
+                     (const mx_e4m3*)ttxt_q, (const float*)tprime_t,
+                     (const float*)bias_t, (__bf16*)g, (float*)ws, b, n, d,
+                     d_t, ldg, diag, alpha, tiles_m, tiles_n,
+                     (const unsigned char*)timg_e8,
+                     (const unsigned char*)ttxt_e8, (int)lde);
   return (int)hipGetLastError();
 }
 

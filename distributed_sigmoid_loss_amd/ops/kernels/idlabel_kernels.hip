@@ -81,10 +81,6 @@ namespace {
 
 enum { G_NONE = 0, G_BF16 = 1, G_E4M3 = 2 };
 
-// Operand element of the MX kernels: an e4m3 byte whose scale lives in a
-// separate e8m0 array (the tile body's zimg_e8 / ztxt_e8 / lde).
-enum mx_e4m3 : unsigned char {};
-
 // 128 row ids and 128 column ids above the g staging, then 4 waves × 3
 // partials.
 constexpr int ids_off(int gfmt) {

@@ -405,6 +405,10 @@ __device__ __forceinline__ void pair_tile_dots_e4m3(
 constexpr int MX_SCALE_BYTES = (BM + BN) * 4;              // one buffer: 1 KiB
 constexpr int MX_LDS_BYTES = 2 * BUF_BYTES + 2 * MX_SCALE_BYTES;   // 66 KiB
 
+// Operand element tag of the kernels that take MX operands: an e4m3 byte
+// whose scale lives in a separate e8m0 array.
+enum mx_e4m3 : unsigned char {};
+
 // d a positive multiple of 32 on top of pair_dims_ok_e4m3, and scale rows of
 // exactly one aligned dword per K-step.
 inline bool pair_dims_ok_mx(const void* zimg_q, const void* zimg_e8,

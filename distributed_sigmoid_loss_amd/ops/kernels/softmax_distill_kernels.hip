@@ -63,6 +63,8 @@
 
 #include "pair_tile.h"
 
+#include <type_traits>
+
 namespace {
 
 // One row's or column's statistics over a tile (or half a tile, in LDS, where
@@ -90,19 +92,45 @@ __device__ __forceinline__ void put_record(Record* dst, float mz, float sz,
   p[1] = float4{x, 0.f, 0.f, 0.f};
 }
 
+// The teacher's K loop by operand element TOP: __bf16, or mx_e4m3 with the
+// block scales in timg_e8 / ttxt_e8, rows lde bytes apart (the true dots of
+// the dequantised values; `lds` then holds MX_LDS_BYTES).
+template <typename TOP>
+__device__ __forceinline__ void teacher_dots(
+    const TOP* __restrict__ timg, const TOP* __restrict__ ttxt,
+    const unsigned char* __restrict__ timg_e8,
+    const unsigned char* __restrict__ ttxt_e8, int b, int n, int d_t, int lde,
+    int m0, int n0, unsigned char* lds, f32x4 (&acc)[4][4]) {
+  if constexpr (std::is_same<TOP, mx_e4m3>::value)
+    pair_tile_dots_mx<true>((const unsigned char*)timg, timg_e8,
+                            (const unsigned char*)ttxt, ttxt_e8, b, n, d_t,
+                            lde, m0, n0, lds, acc);
+  else
+    pair_tile_dots<true>(timg, ttxt, b, n, d_t, m0, n0, lds, acc);
+}
+
+template <typename TOP>
+constexpr int teacher_lds_bytes() {
+  return std::is_same<TOP, mx_e4m3>::value ? MX_LDS_BYTES : 2 * BUF_BYTES;
+}
+
+template <typename TOP = __bf16>
 __launch_bounds__(NTHREADS, 2) __global__ void softmax_distill_stats_kernel(
     const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt,
-    const float* __restrict__ tprime, const __bf16* __restrict__ timg,
-    const __bf16* __restrict__ ttxt, const float* __restrict__ tprime_t,
+    const float* __restrict__ tprime, const TOP* __restrict__ timg,
+    const TOP* __restrict__ ttxt, const float* __restrict__ tprime_t,
     Record* __restrict__ row_ws, Record* __restrict__ col_ws, int b, int n,
-    int d, int d_t, int tiles_m, int tiles_n) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
+    int d, int d_t, int tiles_m, int tiles_n,
+    const unsigned char* __restrict__ timg_e8,
+    const unsigned char* __restrict__ ttxt_e8, int lde) {
+  __shared__ __attribute__((aligned(16))) unsigned char
+      lds[teacher_lds_bytes<TOP>()];
   const TilePos tp = tile_of_block(tiles_m, tiles_n);
   const int m0 = tp.tm * BM, n0 = tp.tn * BN;
 
   // Teacher first; its raw dots wait in registers.
   f32x4 tv[4][4];
-  pair_tile_dots<true>(timg, ttxt, b, n, d_t, m0, n0, lds, tv);
+  teacher_dots(timg, ttxt, timg_e8, ttxt_e8, b, n, d_t, lde, m0, n0, lds, tv);
   f32x4 acc[4][4];
   pair_tile_dots<true>(zimg, ztxt, b, n, d, m0, n0, lds, acc);
 
@@ -301,14 +329,18 @@ __launch_bounds__(NTHREADS) __global__ void softmax_distill_finish_kernel(
 // of the hard positive (hw).  All five or none.
 struct SideVecs { const float *lse_s, *lse_t, *w, *tw, *hw; };
 
+template <typename TOP = __bf16>
 __launch_bounds__(NTHREADS, 2) __global__ void softmax_distill_g_kernel(
     const __bf16* __restrict__ zimg, const __bf16* __restrict__ ztxt,
-    const float* __restrict__ tprime, const __bf16* __restrict__ timg,
-    const __bf16* __restrict__ ttxt, const float* __restrict__ tprime_t,
+    const float* __restrict__ tprime, const TOP* __restrict__ timg,
+    const TOP* __restrict__ ttxt, const float* __restrict__ tprime_t,
     SideVecs rv, SideVecs cv, __bf16* __restrict__ g,
     float* __restrict__ gs_ws, int b, int n, int d, int d_t, long long ldg,
-    int diag, int tiles_m, int tiles_n) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF_BYTES];
+    int diag, int tiles_m, int tiles_n,
+    const unsigned char* __restrict__ timg_e8,
+    const unsigned char* __restrict__ ttxt_e8, int lde) {
+  __shared__ __attribute__((aligned(16))) unsigned char
+      lds[teacher_lds_bytes<TOP>()];
   const TilePos tp = tile_of_block(tiles_m, tiles_n);
   const int m0 = tp.tm * BM, n0 = tp.tn * BN;
 
@@ -322,7 +354,7 @@ __launch_bounds__(NTHREADS, 2) __global__ void softmax_distill_g_kernel(
 
   // Teacher: dots, then the target term in place.
   f32x4 tg[4][4];
-  pair_tile_dots<true>(timg, ttxt, b, n, d_t, m0, n0, lds, tg);
+  teacher_dots(timg, ttxt, timg_e8, ttxt_e8, b, n, d_t, lde, m0, n0, lds, tg);
   {
     const float tc2 = expf(tprime_t[0]) * LOG2E;
     float rl2[4], rtw[4], rhw[4];
@@ -440,13 +472,23 @@ __launch_bounds__(NTHREADS, 2) __global__ void softmax_distill_g_kernel(
   store_g_tile(lds, g, ldg, m0, n0, b, n);
 }
 
-// What both entries check alike: the two pairs, the two temperatures and the
+// The teacher pair as an entry received it: bf16 rows (img, txt; mx false),
+// or MXFP8 — e4m3 rows plus their e8m0 scale rows, lde bytes apart.
+struct Teacher {
+  const void *img, *txt, *img_e8, *txt_e8;
+  long long lde;
+  bool mx;
+};
+
+// What all entries check alike: the two pairs, the two temperatures and the
 // grid size.
 bool dims_ok(const void* zimg, const void* ztxt, const void* tprime,
-             const void* timg, const void* ttxt, const void* tprime_t, int b,
-             int n, int d, int d_t) {
-  if (!pair_dims_ok(zimg, ztxt, b, n, d) ||
-      !pair_dims_ok(timg, ttxt, b, n, d_t))
+             const Teacher& te, const void* tprime_t, int b, int n, int d,
+             int d_t) {
+  if (!pair_dims_ok(zimg, ztxt, b, n, d)) return false;
+  if (te.mx ? !pair_dims_ok_mx(te.img, te.img_e8, te.txt, te.txt_e8, b, n, d_t,
+                               te.lde, te.lde)
+            : !pair_dims_ok(te.img, te.txt, b, n, d_t))
     return false;
   if (tprime == nullptr || tprime_t == nullptr ||
       ((uintptr_t)tprime | (uintptr_t)tprime_t) % 4 != 0)
@@ -465,6 +507,104 @@ int side_state(const void* const* p, int count) {
   }
   if ((given != 0 && given != count) || bits % 4 != 0) return -1;
   return given != 0;
+}
+
+template <typename TOP>
+void launch_stats(hipStream_t stream, const void* zimg, const void* ztxt,
+                  const void* tprime, const Teacher& te, const void* tprime_t,
+                  void* row_ws, void* col_ws, int b, int n, int d, int d_t,
+                  int tiles_m, int tiles_n) {
+  hipLaunchKernelGGL(softmax_distill_stats_kernel<TOP>,
+                     dim3(tiles_m * tiles_n), dim3(NTHREADS), 0, stream,
+                     (const __bf16*)zimg, (const __bf16*)ztxt,
+                     (const float*)tprime, (const TOP*)te.img,
+                     (const TOP*)te.txt, (const float*)tprime_t,
+                     (Record*)row_ws, (Record*)col_ws, b, n, d, d_t, tiles_m,
+                     tiles_n, (const unsigned char*)te.img_e8,
+                     (const unsigned char*)te.txt_e8, (int)te.lde);
+}
+
+int stats_entry(uintptr_t stream, const void* zimg, const void* ztxt,
+                const void* tprime, const Teacher& te, const void* tprime_t,
+                void* row_ws, void* col_ws, void* row_lse_s, void* row_lse_t,
+                void* row_x, void* col_lse_s, void* col_lse_t, void* col_x,
+                int b, int n, int d, int d_t) {
+  if (!dims_ok(zimg, ztxt, tprime, te, tprime_t, b, n, d, d_t))
+    return (int)hipErrorInvalidValue;
+  const void* const rp[4] = {row_ws, row_lse_s, row_lse_t, row_x};
+  const void* const cp[4] = {col_ws, col_lse_s, col_lse_t, col_x};
+  const int rows = side_state(rp, 4), cols = side_state(cp, 4);
+  if (rows < 0 || cols < 0 ||
+      ((uintptr_t)row_ws | (uintptr_t)col_ws) % 16 != 0)
+    return (int)hipErrorInvalidValue;
+  if (!rows && !cols) return 0;
+  const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
+  if (te.mx)
+    launch_stats<mx_e4m3>((hipStream_t)stream, zimg, ztxt, tprime, te,
+                          tprime_t, row_ws, col_ws, b, n, d, d_t, tiles_m,
+                          tiles_n);
+  else
+    launch_stats<__bf16>((hipStream_t)stream, zimg, ztxt, tprime, te,
+                         tprime_t, row_ws, col_ws, b, n, d, d_t, tiles_m,
+                         tiles_n);
+  int rc = (int)hipGetLastError();
+  if (rc != 0) return rc;
+  const long long ids = (rows ? (long long)b : 0) + (cols ? (long long)n : 0);
+  hipLaunchKernelGGL(softmax_distill_finish_kernel,
+                     dim3((unsigned)((ids + NTHREADS - 1) / NTHREADS)),
+                     dim3(NTHREADS), 0, (hipStream_t)stream,
+                     (const Record*)row_ws, (const Record*)col_ws,
+                     StatsOut{(float*)row_lse_s, (float*)row_lse_t,
+                              (float*)row_x},
+                     StatsOut{(float*)col_lse_s, (float*)col_lse_t,
+                              (float*)col_x},
+                     b, n, tiles_m, tiles_n);
+  return (int)hipGetLastError();
+}
+
+template <typename TOP>
+void launch_g(hipStream_t stream, const void* zimg, const void* ztxt,
+              const void* tprime, const Teacher& te, const void* tprime_t,
+              SideVecs rv, SideVecs cv, void* g, void* gs_ws, int b, int n,
+              int d, int d_t, long long ldg, int diag, int tiles_m,
+              int tiles_n) {
+  hipLaunchKernelGGL(softmax_distill_g_kernel<TOP>, dim3(tiles_m * tiles_n),
+                     dim3(NTHREADS), 0, stream, (const __bf16*)zimg,
+                     (const __bf16*)ztxt, (const float*)tprime,
+                     (const TOP*)te.img, (const TOP*)te.txt,
+                     (const float*)tprime_t, rv, cv, (__bf16*)g,
+                     (float*)gs_ws, b, n, d, d_t, ldg, diag, tiles_m, tiles_n,
+                     (const unsigned char*)te.img_e8,
+                     (const unsigned char*)te.txt_e8, (int)te.lde);
+}
+
+// row / col: (lse_s, lse_t, w, tw, hw) of the side.
+int g_entry(uintptr_t stream, const void* zimg, const void* ztxt,
+            const void* tprime, const Teacher& te, const void* tprime_t,
+            const void* const (&rp)[5], const void* const (&cp)[5], void* g,
+            void* gs_ws, int b, int n, int d, int d_t, long long ldg,
+            int diag) {
+  if (!dims_ok(zimg, ztxt, tprime, te, tprime_t, b, n, d, d_t) ||
+      g == nullptr || gs_ws == nullptr || ldg < n)
+    return (int)hipErrorInvalidValue;
+  if (side_state(rp, 5) < 0 || side_state(cp, 5) < 0 ||
+      (uintptr_t)gs_ws % 4 != 0 || (uintptr_t)g % 2 != 0)
+    return (int)hipErrorInvalidValue;
+  const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
+  const SideVecs rv{(const float*)rp[0], (const float*)rp[1],
+                    (const float*)rp[2], (const float*)rp[3],
+                    (const float*)rp[4]};
+  const SideVecs cv{(const float*)cp[0], (const float*)cp[1],
+                    (const float*)cp[2], (const float*)cp[3],
+                    (const float*)cp[4]};
+  if (te.mx)
+    launch_g<mx_e4m3>((hipStream_t)stream, zimg, ztxt, tprime, te, tprime_t,
+                      rv, cv, g, gs_ws, b, n, d, d_t, ldg, diag, tiles_m,
+                      tiles_n);
+  else
+    launch_g<__bf16>((hipStream_t)stream, zimg, ztxt, tprime, te, tprime_t, rv,
+                     cv, g, gs_ws, b, n, d, d_t, ldg, diag, tiles_m, tiles_n);
+  return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -490,36 +630,30 @@ int softmax_distill_stats_bf16(uintptr_t stream, const void* zimg,
                                void* col_ws, void* row_lse_s, void* row_lse_t,
                                void* row_x, void* col_lse_s, void* col_lse_t,
                                void* col_x, int b, int n, int d, int d_t) {
-  if (!dims_ok(zimg, ztxt, tprime, timg, ttxt, tprime_t, b, n, d, d_t))
-    return (int)hipErrorInvalidValue;
-  const void* const rp[4] = {row_ws, row_lse_s, row_lse_t, row_x};
-  const void* const cp[4] = {col_ws, col_lse_s, col_lse_t, col_x};
-  const int rows = side_state(rp, 4), cols = side_state(cp, 4);
-  if (rows < 0 || cols < 0 ||
-      ((uintptr_t)row_ws | (uintptr_t)col_ws) % 16 != 0)
-    return (int)hipErrorInvalidValue;
-  if (!rows && !cols) return 0;
-  const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
-  hipLaunchKernelGGL(softmax_distill_stats_kernel, dim3(tiles_m * tiles_n),
-                     dim3(NTHREADS), 0, (hipStream_t)stream,
-                     (const __bf16*)zimg, (const __bf16*)ztxt,
-                     (const float*)tprime, (const __bf16*)timg,
-                     (const __bf16*)ttxt, (const float*)tprime_t,
-                     (Record*)row_ws, (Record*)col_ws, b, n, d, d_t, tiles_m,
-                     tiles_n);
-  int rc = (int)hipGetLastError();
-  if (rc != 0) return rc;
-  const long long ids = (rows ? (long long)b : 0) + (cols ? (long long)n : 0);
-  hipLaunchKernelGGL(softmax_distill_finish_kernel,
-                     dim3((unsigned)((ids + NTHREADS - 1) / NTHREADS)),
-                     dim3(NTHREADS), 0, (hipStream_t)stream,
-                     (const Record*)row_ws, (const Record*)col_ws,
-                     StatsOut{(float*)row_lse_s, (float*)row_lse_t,
-                              (float*)row_x},
-                     StatsOut{(float*)col_lse_s, (float*)col_lse_t,
-                              (float*)col_x},
-                     b, n, tiles_m, tiles_n);
-  return (int)hipGetLastError();
+  return stats_entry(stream, zimg, ztxt, tprime,
+                     Teacher{timg, ttxt, nullptr, nullptr, 0, false}, tprime_t,
+                     row_ws, col_ws, row_lse_s, row_lse_t, row_x, col_lse_s,
+                     col_lse_t, col_x, b, n, d, d_t);
+}
+
+// The same with an MXFP8 teacher pair: timg_q (b, d_t), ttxt_q (n, d_t) OCP
+// e4m3fn bytes, row-major contiguous, d_t a multiple of 32; timg_e8 (b rows),
+// ttxt_e8 (n rows) their e8m0 block scales, byte kb of a row for elements
+// 32·kb … +31, 4-byte aligned with rows lde bytes apart, exactly
+// 4·ceil(d_t / 128).  v is exp(*tprime_t) times the true dot of the
+// dequantised values: tprime_t is passed unchanged.
+int softmax_distill_stats_mxt(uintptr_t stream, const void* zimg,
+                              const void* ztxt, const void* tprime,
+                              const void* timg_q, const void* timg_e8,
+                              const void* ttxt_q, const void* ttxt_e8,
+                              const void* tprime_t, void* row_ws, void* col_ws,
+                              void* row_lse_s, void* row_lse_t, void* row_x,
+                              void* col_lse_s, void* col_lse_t, void* col_x,
+                              int b, int n, int d, int d_t, long long lde) {
+  return stats_entry(stream, zimg, ztxt, tprime,
+                     Teacher{timg_q, ttxt_q, timg_e8, ttxt_e8, lde, true},
+                     tprime_t, row_ws, col_ws, row_lse_s, row_lse_t, row_x,
+                     col_lse_s, col_lse_t, col_x, b, n, d, d_t);
 }
 
 // g (b, n) bf16 with row stride ldg elements, and gs_ws[tile] = Σ g_ij·s_ij
@@ -536,29 +670,31 @@ int softmax_distill_g_bf16(uintptr_t stream, const void* zimg,
                            const void* col_w, const void* col_tw,
                            const void* col_hw, void* g, void* gs_ws, int b,
                            int n, int d, int d_t, long long ldg, int diag) {
-  if (!dims_ok(zimg, ztxt, tprime, timg, ttxt, tprime_t, b, n, d, d_t) ||
-      g == nullptr || gs_ws == nullptr || ldg < n)
-    return (int)hipErrorInvalidValue;
   const void* const rp[5] = {row_lse_s, row_lse_t, row_w, row_tw, row_hw};
   const void* const cp[5] = {col_lse_s, col_lse_t, col_w, col_tw, col_hw};
-  if (side_state(rp, 5) < 0 || side_state(cp, 5) < 0 ||
-      (uintptr_t)gs_ws % 4 != 0 || (uintptr_t)g % 2 != 0)
-    return (int)hipErrorInvalidValue;
-  const int tiles_m = ceil_div(b, BM), tiles_n = ceil_div(n, BN);
-  const SideVecs rv{(const float*)row_lse_s, (const float*)row_lse_t,
-                    (const float*)row_w, (const float*)row_tw,
-                    (const float*)row_hw};
-  const SideVecs cv{(const float*)col_lse_s, (const float*)col_lse_t,
-                    (const float*)col_w, (const float*)col_tw,
-                    (const float*)col_hw};
-  hipLaunchKernelGGL(softmax_distill_g_kernel, dim3(tiles_m * tiles_n),
-                     dim3(NTHREADS), 0, (hipStream_t)stream,
-                     (const __bf16*)zimg, (const __bf16*)ztxt,
-                     (const float*)tprime, (const __bf16*)timg,
-                     (const __bf16*)ttxt, (const float*)tprime_t, rv, cv,
-                     (__bf16*)g, (float*)gs_ws, b, n, d, d_t, ldg, diag,
-                     tiles_m, tiles_n);
-  return (int)hipGetLastError();
+  return g_entry(stream, zimg, ztxt, tprime,
+                 Teacher{timg, ttxt, nullptr, nullptr, 0, false}, tprime_t, rp,
+                 cp, g, gs_ws, b, n, d, d_t, ldg, diag);
+}
+
+// The same with the MXFP8 teacher pair of softmax_distill_stats_mxt.
+int softmax_distill_g_mxt(uintptr_t stream, const void* zimg,
+                          const void* ztxt, const void* tprime,
+                          const void* timg_q, const void* timg_e8,
+                          const void* ttxt_q, const void* ttxt_e8,
+                          const void* tprime_t, const void* row_lse_s,
+                          const void* row_lse_t, const void* row_w,
+                          const void* row_tw, const void* row_hw,
+                          const void* col_lse_s, const void* col_lse_t,
+                          const void* col_w, const void* col_tw,
+                          const void* col_hw, void* g, void* gs_ws, int b,
+                          int n, int d, int d_t, long long lde, long long ldg,
+                          int diag) {
+  const void* const rp[5] = {row_lse_s, row_lse_t, row_w, row_tw, row_hw};
+  const void* const cp[5] = {col_lse_s, col_lse_t, col_w, col_tw, col_hw};
+  return g_entry(stream, zimg, ztxt, tprime,
+                 Teacher{timg_q, ttxt_q, timg_e8, ttxt_e8, lde, true},
+                 tprime_t, rp, cp, g, gs_ws, b, n, d, d_t, ldg, diag);
 }
 
 }  // extern "C"

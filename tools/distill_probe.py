@@ -6,8 +6,10 @@ against the chunked torch composite it replaces, in one process.
                                   [--teacher-dim 768] [--alpha 0.5]
                                   [--iters 30] [--stock-iters 5]
                                   [--only all|loss|g]
+                                  [--teacher-quant bf16|mxfp8]
 
-At each (B, B, d / d_T) bf16 shape: L2-normalised student and teacher rows,
+``--teacher-quant mxfp8`` times the MXFP8-teacher kernel against the
+bf16-teacher kernel instead (``probe_mx``).  At each (B, B, d / d_T) bf16 shape: L2-normalised student and teacher rows,
 ``t = t_T = 10``, ``bias = bias_T = −10``, ``diag_offset = 0``.  Every timing
 is the median (with min and max) of warm calls timed one by one between device
 events; the two sides of a pair are timed alternately, call by call, so that
@@ -107,6 +109,61 @@ def probe(b, d, d_t, alpha, iters, stock_iters, only):
     return out
 
 
+def probe_mx(b, d, d_t, alpha, iters, stock_iters):
+    """``--teacher-quant mxfp8``: the MX-teacher kernel against the
+    bf16-teacher kernel on the same teacher, alternated call by call; the cost
+    of ``ops.quantize_mx`` on one ``(B, d_T)`` shard; the forward + backward
+    with a stored ``(q, e8)`` teacher against the bf16 one."""
+    gen = torch.Generator(device="cuda").manual_seed(0)
+
+    def rows(dim):
+        return F.normalize(torch.randn(b, dim, device="cuda", generator=gen),
+                           dim=-1).bfloat16()
+
+    zi, zt, ti, tt = rows(d), rows(d), rows(d_t), rows(d_t)
+    tp = torch.tensor(math.log(10.0), device="cuda")
+    bias = torch.tensor(-10.0, device="cuda")
+    pairs = ops.quantize_mx(ti), ops.quantize_mx(tt)
+    tail = (tp.clone(), bias.clone(), alpha, 0)
+    out = {"probe": "distill_mx_teacher", "batch": b, "dim": d,
+           "teacher_dim": d_t, "alpha": alpha, "iters": iters,
+           "device": torch.cuda.get_device_name(0)}
+
+    def put(name, stats):
+        out.update({f"{name}_ms": stats[0], f"{name}_min_ms": stats[1],
+                    f"{name}_max_ms": stats[2]})
+
+    put("quantize_mx", median_ms(lambda: ops.quantize_mx(ti), iters))
+    g_buf = torch.empty((b, b), device="cuda", dtype=torch.bfloat16)
+    for name, kw in (("loss", dict(want_g=False)), ("g", dict(g=g_buf))):
+        mx, bf = alternate_ms(
+            lambda: ops.sigmoid_distill_mx(zi, zt, tp, bias, *pairs[0],
+                                           *pairs[1], *tail, **kw),
+            lambda: ops.sigmoid_distill(zi, zt, tp, bias, ti, tt, *tail,
+                                        **kw), iters)
+        put(f"mx_{name}", mx)
+        put(f"bf16_{name}", bf)
+        out[f"mx_over_bf16_{name}"] = round(
+            out[f"mx_{name}_ms"] / out[f"bf16_{name}_ms"], 3)
+    del g_buf
+
+    leaves = [x.clone().requires_grad_() for x in (zi, zt, tp, bias)]
+
+    def step(ti, tt, quant):
+        def run():
+            for x in leaves:
+                x.grad = None
+            sigmoid_distillation_loss(*leaves, ti, tt, *tail, impl="hip",
+                                      teacher_quant=quant).backward()
+        return run
+
+    mx, bf = alternate_ms(step(*pairs, "mxfp8"), step(ti, tt, "bf16"),
+                          stock_iters, warmup=2)
+    put("mx_fused", mx)
+    put("bf16_fused", bf)
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, nargs="+", default=[32768, 8192])
@@ -116,15 +173,21 @@ def main():
     p.add_argument("--iters", type=int, default=30)
     p.add_argument("--stock-iters", type=int, default=5)
     p.add_argument("--only", choices=["all", "loss", "g"], default="all")
+    p.add_argument("--teacher-quant", choices=["bf16", "mxfp8"],
+                   default="bf16")
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("distill_probe needs a GPU")
     if args.iters < 20:
         raise SystemExit("--iters must be at least 20")
     for b in args.batch:
-        print(json.dumps(probe(b, args.dim, args.teacher_dim, args.alpha,
-                               args.iters, args.stock_iters, args.only)),
-              flush=True)
+        if args.teacher_quant == "mxfp8":
+            res = probe_mx(b, args.dim, args.teacher_dim, args.alpha,
+                           args.iters, args.stock_iters)
+        else:
+            res = probe(b, args.dim, args.teacher_dim, args.alpha,
+                        args.iters, args.stock_iters, args.only)
+        print(json.dumps(res), flush=True)
         torch.cuda.empty_cache()
 
 

@@ -7,8 +7,10 @@ process.
                                           [--teacher-dim 768] [--alpha 0.5]
                                           [--iters 30] [--stock-iters 5]
                                           [--only all|stats|g]
+                                          [--teacher-quant bf16|mxfp8]
 
-At each (B, B, d / d_T) bf16 shape: L2-normalised student and teacher rows,
+``--teacher-quant mxfp8`` times the MXFP8-teacher ops against the
+bf16-teacher ops instead (``probe_mx``).  At each (B, B, d / d_T) bf16 shape: L2-normalised student and teacher rows,
 ``t = t_T = 10``, ``diag_offset = 0``.  Every timing is the median (with min
 and max) of warm calls timed one by one between device events; the two sides
 of a pair are timed alternately, call by call, so that drift of the clocks
@@ -117,6 +119,44 @@ def probe(b, d, d_t, alpha, iters, stock_iters, only):
     return out
 
 
+def probe_mx(b, d, d_t, alpha, iters):
+    """``--teacher-quant mxfp8``: the two MX-teacher ops against the
+    bf16-teacher ops on the same teacher, alternated call by call."""
+    gen = torch.Generator(device="cuda").manual_seed(0)
+
+    def rows(dim):
+        return F.normalize(torch.randn(b, dim, device="cuda", generator=gen),
+                           dim=-1).bfloat16()
+
+    zi, zt, ti, tt = rows(d), rows(d), rows(d_t), rows(d_t)
+    tp = torch.tensor(math.log(10.0), device="cuda")
+    mx = (*ops.quantize_mx(ti), *ops.quantize_mx(tt))
+    out = {"probe": "softmax_distill_mx_teacher", "batch": b, "dim": d,
+           "teacher_dim": d_t, "alpha": alpha, "iters": iters,
+           "device": torch.cuda.get_device_name(0)}
+    st = ops.pair_distill_stats(zi, zt, tp, ti, tt, tp)
+    tw = torch.full((b,), alpha, device="cuda")
+    hw = torch.full((b,), 1.0 - alpha, device="cuda")
+    row = (st.row_lse_s, st.row_lse_t, tw + hw, tw, hw)
+    col = (st.col_lse_s, st.col_lse_t, tw + hw, tw, hw)
+    g_buf = torch.empty((b, b), device="cuda", dtype=torch.bfloat16)
+    pairs = (
+        ("stats", lambda: ops.pair_distill_stats_mx(zi, zt, tp, *mx, tp),
+         lambda: ops.pair_distill_stats(zi, zt, tp, ti, tt, tp)),
+        ("g", lambda: ops.softmax_distill_g_mx(zi, zt, tp, *mx, tp, row, col,
+                                               0, g=g_buf),
+         lambda: ops.softmax_distill_g(zi, zt, tp, ti, tt, tp, row, col, 0,
+                                       g=g_buf)))
+    for name, mx_fn, bf_fn in pairs:
+        for key, stats in zip((f"mx_{name}", f"bf16_{name}"),
+                              alternate_ms(mx_fn, bf_fn, iters)):
+            out.update({f"{key}_ms": stats[0], f"{key}_min_ms": stats[1],
+                        f"{key}_max_ms": stats[2]})
+        out[f"mx_over_bf16_{name}"] = round(
+            out[f"mx_{name}_ms"] / out[f"bf16_{name}_ms"], 3)
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--batch", type=int, nargs="+", default=[32768, 8192])
@@ -126,15 +166,21 @@ def main():
     p.add_argument("--iters", type=int, default=30)
     p.add_argument("--stock-iters", type=int, default=5)
     p.add_argument("--only", choices=["all", "stats", "g"], default="all")
+    p.add_argument("--teacher-quant", choices=["bf16", "mxfp8"],
+                   default="bf16")
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("softmax_distill_probe needs a GPU")
     if args.iters < 20:
         raise SystemExit("--iters must be at least 20")
     for b in args.batch:
-        print(json.dumps(probe(b, args.dim, args.teacher_dim, args.alpha,
-                               args.iters, args.stock_iters, args.only)),
-              flush=True)
+        if args.teacher_quant == "mxfp8":
+            res = probe_mx(b, args.dim, args.teacher_dim, args.alpha,
+                           args.iters)
+        else:
+            res = probe(b, args.dim, args.teacher_dim, args.alpha,
+                        args.iters, args.stock_iters, args.only)
+        print(json.dumps(res), flush=True)
         torch.cuda.empty_cache()
 
 
